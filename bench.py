@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end voice-conversion throughput of the MI355X path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--inflight M]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--inflight M] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic utterance: `Pipeline.pipeline` from the 16 kHz input array to
 the float32 waveform at the model's rate.  `--config` picks the BASELINE.json configuration (default 2, the one the
@@ -22,7 +22,15 @@ its own utterances (utterance i -> rank i mod N); the index is built on rank 0 a
 through the C ABI (rvc_index_broadcast) and verified by a device-side checksum; the steady state has no collective
 ("scaling": "weak").  On each GPU `--inflight` utterances (default 3) are in flight at a time, each on its own HIP stream.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` then also writes the waveform of
+the last timed step's utterance to DIR/waveform.npy (float32: 5.8 MB for a 30 s clip at 48 kHz; a seeded sample of 64 MB
+for a clip too long for that), so that two builds can be compared output for output.  The utterances in flight share the
+device's noise generator, so the draws a timed step gets depend on thread timing; the dumped waveform is therefore that same
+utterance converted once more through the same call after the timed steps, with the device generator seeded (one in
+flight), so that equal arguments give equal inputs and equal noise draws in every run.
+
+Rank 0 prints ONE JSON line.  Everything below is measured only with `--full` (off by default; `--no-rooflines` and
+`--no-cpu-baseline` leave a leg out of a --full run); a plain run reports these fields as null or leaves them out:
   roofline      the dominant kernel symbol (the 11-tap ResBlock convs of vocoder stages 0-2: Winograd F(4,4) on the bf16 matrix
                 cores with fp32 operands split exactly into three bf16), timed live with HIP events on the launch stream
   roofline_knn  the L2 top-8 search at this config's (queries x rows): the fp16-screened regime, `frac` = its fp16 MFMA fraction
@@ -100,6 +108,12 @@ def parse_args(argv=None):
                     help="clip length of the CPU-baseline sample (default: the config's own clip length, i.e. the same "
                          "synthetic input as the GPU run; e.g. 3 for a quick bounded sample)")
     ap.add_argument("--cpu-threads", type=int, default=None, help="torch threads of the CPU baseline (default min(host cpus, 32))")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the host-array (PCIe-inclusive) pass, the per-kernel roofline legs and the CPU baseline "
+                         "(off: the run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's waveform to DIR/waveform.npy (float32; "
+                         "recomputed with the device noise generator seeded, so equal arguments give equal inputs and draws)")
     ap.add_argument("--control-flow-only", action="store_true",
                     help="CPU test hook: run the launcher / process-group / sharding / broadcast / report path over gloo "
                          "without any kernel (no throughput is measured; the line says so)")
@@ -107,6 +121,13 @@ def parse_args(argv=None):
     if args.steps is None:
         args.steps = max(1, CONFIGS[args.config].get("batch", 20 * max(1, args.gpus)) // max(1, args.gpus))
     return args
+
+
+def extra_legs(args, world):
+    """What this run measures besides the headline: nothing unless --full (a plain run sets up, warms up, times the steps and
+    reports); --no-rooflines / --no-cpu-baseline leave a leg out of a --full run, and the CPU baseline is a 1-GPU figure."""
+    return {"host_io": args.full, "rooflines": args.full and not args.no_rooflines,
+            "cpu_baseline": args.full and world == 1 and not args.no_cpu_baseline}
 
 
 def cpu_model_string():
@@ -331,22 +352,28 @@ def main():
     out_len = int(outs[-1].shape[0])
     del outs
 
-    # the boundary as the reference has it: host NumPy in, host float32 NumPy out (PCIe inclusive), same schedule
-    run_steps(audios_host, 0, 2 * inflight)   # every stream touches both of its page-locked slots once
-    torch.cuda.synchronize()
-    t_host = None
-    for _ in range(2):                        # best of two passes of K steps: a one-off host stall must not pose as PCIe cost
-        t0 = time.perf_counter()
-        houts = run_steps(audios_host, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_last_step(torch, vc, audios[(args.warmup + args.steps - 1) % len(audios)], kw, dev, args.dump_outputs)
+
+    legs = extra_legs(args, world)
+    host_io = None
+    if legs["host_io"]:
+        # the boundary as the reference has it: host NumPy in, host float32 NumPy out (PCIe inclusive), same schedule
+        run_steps(audios_host, 0, 2 * inflight)   # every stream touches both of its page-locked slots once
         torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        t_host = dt if t_host is None else min(t_host, dt)
-    assert all(isinstance(o, np.ndarray) and o.dtype == np.float32 and np.isfinite(o).all() for o in houts)
-    host_io = {"samples_per_s_rank0": round(sum(o.shape[0] for o in houts) / t_host, 1),
-               "ms_per_step": round(t_host / args.steps * 1e3, 2), "inflight": inflight,
-               "what": "same K steps (best of two passes), 16 kHz float64 NumPy array in host memory -> float32 NumPy waveform in host "
-                       "memory (the reference's Pipeline.pipeline boundary, pipeline.py:509-528)"}
-    del houts
+        t_host = None
+        for _ in range(2):                        # best of two passes of K steps: a one-off host stall must not pose as PCIe cost
+            t0 = time.perf_counter()
+            houts = run_steps(audios_host, args.warmup, args.steps)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            t_host = dt if t_host is None else min(t_host, dt)
+        assert all(isinstance(o, np.ndarray) and o.dtype == np.float32 and np.isfinite(o).all() for o in houts)
+        host_io = {"samples_per_s_rank0": round(sum(o.shape[0] for o in houts) / t_host, 1),
+                   "ms_per_step": round(t_host / args.steps * 1e3, 2), "inflight": inflight,
+                   "what": "same K steps (best of two passes), 16 kHz float64 NumPy array in host memory -> float32 NumPy waveform in host "
+                           "memory (the reference's Pipeline.pipeline boundary, pipeline.py:509-528)"}
+        del houts
 
     if rank != 0:
         barrier()
@@ -377,8 +404,9 @@ def main():
                  "products of order <= 2^-16 per multiply-add, fp32 accumulate; everything else fp32 / fp64)",
         "data": "synthetic (seeded random-init weights, FM-tone utterances, clustered index)",
         "rtf": round(value / sr, 2),
-        "headline_is": "inputs resident in HBM, waveform left in HBM (the bench contract's definition of `value`); `host_io` is the "
-                       "same run through the reference's host-array boundary and is the figure to quote for a drop-in user",
+        "headline_is": "inputs resident in HBM, waveform left in HBM (the bench contract's definition of `value`); `host_io` (--full) is "
+                       "the same run through the reference's host-array boundary and is the figure to quote for a drop-in user",
+        "full": args.full,
         "config": {"workload": f"{cfg['name']}; rmvpe, protect 0.5; 1 utterance per step per GPU, {inflight} utterance(s) in "
                                f"flight per GPU on separate HIP streams" + (f"; clip {cfg['seconds']:g} s" if args.seconds else ""),
                    "baseline_config": args.config,
@@ -401,11 +429,11 @@ def main():
                  "torch_threads": torch.get_num_threads(), "python_threads_per_rank": inflight + 1, "ranks": world},
     }
 
-    if not args.no_rooflines:
+    if legs["rooflines"]:
         line.update(rooflines(torch, _native, vc, cpt, cfg, dev, n_in, index_dev, audios[0]))
 
     # ---- CPU baseline: the oracle on the host cores, on the SAME synthetic utterance and index the GPU run used ----
-    if world == 1 and not args.no_cpu_baseline:
+    if legs["cpu_baseline"]:
         line["cpu_baseline"] = cpu_baseline(torch, S, cfg, cpt, args, index_dev, sr)
     else:
         line["cpu_baseline"] = None
@@ -419,6 +447,22 @@ def main():
             torch.distributed.destroy_process_group()
     if rank == 0:
         print(json.dumps(line), flush=True)
+
+
+DUMP_MAX_VALUES = 16_000_000   # float32 values per dump: 64 MB at most
+
+
+def dump_last_step(torch, vc, utterance, kw, dev, out_dir):
+    """--dump-outputs: the last timed step's utterance through the timed call once more, one in flight, with the device noise
+    generator seeded -> out_dir/waveform.npy (float32; a seeded sample of DUMP_MAX_VALUES values, in order, if longer)."""
+    torch.cuda.manual_seed(1234)
+    (wave,) = vc.convert_batch([utterance], inflight=1, **kw)
+    torch.cuda.synchronize(dev)
+    w = wave.float().cpu().numpy()
+    if w.size > DUMP_MAX_VALUES:
+        w = w[np.sort(np.random.default_rng(0).choice(w.size, DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "waveform.npy"), np.ascontiguousarray(w, dtype=np.float32))
 
 
 def cpu_baseline(torch, S, cfg, cpt, args, index_dev, sr):

@@ -81,3 +81,66 @@ def test_checksum_formula_host():
     n, w = 1 << 20, 0xFFFFFFFF
     assert s1 == (n * w) % (1 << 64) and s2 == (w * n * (n + 1) // 2) % (1 << 64)
     assert tensor_checksum(torch.tensor([1.0, 2.0])) != tensor_checksum(torch.tensor([2.0, 1.0]))   # order matters
+
+
+
+def _bench():
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    import bench
+    return bench
+
+
+def test_bench_args_steps_as_given_full_and_dump_off_by_default():
+    """`--steps` sets the timed steps as given (config 3 included); `--full` and `--dump-outputs` are off unless named."""
+    bench = _bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--config", "3", "--steps", "5", "--full", "--dump-outputs", "d"])
+    assert a.steps == 5 and a.full and a.dump_outputs == "d"
+
+
+def test_bench_plain_run_measures_no_extra_legs():
+    """What main() runs besides the headline (bench.extra_legs): nothing in a plain run, every leg with --full, and
+    --no-rooflines / --no-cpu-baseline still leave theirs out; the CPU baseline is a 1-GPU figure."""
+    bench = _bench()
+    plain = bench.extra_legs(bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]), 1)
+    assert plain == {"host_io": False, "rooflines": False, "cpu_baseline": False}
+    full = bench.extra_legs(bench.parse_args(["--full"]), 1)
+    assert full == {"host_io": True, "rooflines": True, "cpu_baseline": True}
+    some = bench.extra_legs(bench.parse_args(["--full", "--no-rooflines", "--no-cpu-baseline"]), 1)
+    assert some == {"host_io": True, "rooflines": False, "cpu_baseline": False}
+    assert not bench.extra_legs(bench.parse_args(["--full", "--gpus", "2"]), 2)["cpu_baseline"]
+
+
+def test_bench_dump_last_step_writes_seeded_float32(tmp_path, monkeypatch):
+    """--dump-outputs (bench.dump_last_step) with a stub converter and stubbed torch.cuda: the device generator is seeded
+    BEFORE the one conversion, that conversion runs one in flight with the timed call's arguments, and DIR/waveform.npy is
+    the float32 waveform -- or, above DUMP_MAX_VALUES, the same seeded, ordered sample in every run."""
+    from types import SimpleNamespace
+    bench = _bench()
+    calls = []
+    fake_torch = SimpleNamespace(cuda=SimpleNamespace(manual_seed=lambda s: calls.append(("seed", s)),
+                                                      synchronize=lambda dev=None: calls.append(("sync", dev))))
+
+    class VC:
+        def __init__(self, wave):
+            self.wave = wave
+
+        def convert_batch(self, audios, inflight, **kw):
+            calls.append(("convert", len(audios), inflight, kw))
+            return [self.wave]
+
+    kw = dict(index_path="", index_rate=0.75, protect=0.5, sid=0)
+    wave = torch.linspace(-0.5, 0.5, 5000, dtype=torch.float64)
+    bench.dump_last_step(fake_torch, VC(wave), torch.zeros(16000), kw, "cuda:0", str(tmp_path / "d"))
+    assert calls[0][0] == "seed" and calls[1] == ("convert", 1, 1, kw) and calls[2] == ("sync", "cuda:0")
+    got = np.load(tmp_path / "d" / "waveform.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, wave.numpy().astype(np.float32))
+
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    for d in ("a", "b"):
+        bench.dump_last_step(fake_torch, VC(wave), torch.zeros(16000), kw, "cuda:0", str(tmp_path / d))
+    a, b = np.load(tmp_path / "a" / "waveform.npy"), np.load(tmp_path / "b" / "waveform.npy")
+    assert a.dtype == np.float32 and a.shape == (1000,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.isin(a, wave.numpy().astype(np.float32)).all()   # an ordered subset of the waveform

@@ -12,6 +12,18 @@ from conftest import load_golden, rms
 from oracle import rvc_oracle as O
 from rvc_amd.lib import synthetic as S
 
+
+@pytest.fixture(autouse=True)
+def _pinned_thread_count():
+    """The oracle's float32 CPU results move with torch's intra-op thread count (the split of its reductions): at 1, 4, 16
+    or 64 threads the RMVPE salience / hidden layer land up to 5.7e-5 from the fixtures, against gates of 2e-5 set at 8.
+    Every check here runs at 8 threads, whatever the session uses (conftest.py raises it while the oracle farm works)."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 SYNTH_CASES = [("nsf48", 48000, "HiFi-GAN"), ("nsf40", 40000, "HiFi-GAN"), ("nsf32", 32000, "HiFi-GAN"),
                ("mrf48", 48000, "MRF HiFi-GAN"), ("refine48", 48000, "RefineGAN")]
 

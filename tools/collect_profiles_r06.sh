@@ -10,14 +10,14 @@
 R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 O=$R/gpurun_out/r06p; P=$R/gpurun_out/r06p/profiles; mkdir -p $O $P
 cp $R/profiles/pmc_*.json $P/ 2>/dev/null
-python3 $R/bench.py --config 2 --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-python3 $R/bench.py --config 4 --steps 20 --warmup 5 --cpu-seconds 3 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-python3 $R/bench.py --config 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg2_again.json 2>/dev/null
-python3 $R/bench.py --config 4 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg4_again.json 2>/dev/null
-for c in 1 5; do python3 $R/bench.py --config $c --steps 20 --warmup 5 --cpu-seconds 3 > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; done
-python3 $R/bench.py --config 2 --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline > $O/bench_cfg2_inflight1.json 2>/dev/null
-python3 $R/bench.py --config 2 --steps 20 --warmup 5 --inflight 2 --no-cpu-baseline --no-rooflines > $O/bench_cfg2_inflight2.json 2>/dev/null
-python3 $R/bench.py --config 2 --seconds 100 --steps 8 --warmup 2 --no-cpu-baseline --no-rooflines > $O/bench_cfg2_100s.json 2> $O/bench_cfg2_100s.err
+python3 $R/bench.py --full --config 2 --steps 20 --warmup 5 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+python3 $R/bench.py --full --config 4 --steps 20 --warmup 5 --cpu-seconds 3 > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+python3 $R/bench.py --full --config 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg2_again.json 2>/dev/null
+python3 $R/bench.py --full --config 4 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_cfg4_again.json 2>/dev/null
+for c in 1 5; do python3 $R/bench.py --full --config $c --steps 20 --warmup 5 --cpu-seconds 3 > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; done
+python3 $R/bench.py --full --config 2 --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline > $O/bench_cfg2_inflight1.json 2>/dev/null
+python3 $R/bench.py --full --config 2 --steps 20 --warmup 5 --inflight 2 --no-cpu-baseline --no-rooflines > $O/bench_cfg2_inflight2.json 2>/dev/null
+python3 $R/bench.py --full --config 2 --seconds 100 --steps 8 --warmup 2 --no-cpu-baseline --no-rooflines > $O/bench_cfg2_100s.json 2> $O/bench_cfg2_100s.err
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o b -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_under_rocprof.log 2>&1
 cp /tmp/pb/b_kernel_stats.csv $O/bench_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb1 -o b -- python3 $R/bench.py --steps 10 --warmup 3 --inflight 1 --no-cpu-baseline > $O/bench_under_rocprof_inflight1.log 2>&1
