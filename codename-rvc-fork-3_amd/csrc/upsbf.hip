@@ -16,7 +16,9 @@
 //     fragments LDS -> registers double-buffered, six products per multiply-add, smallest first, fp32 accumulate;
 //   * epilogue: accumulators + bias -> an LDS tile [channel][q r + ph] (the interleave happens here), which the stagers drain with coalesced
 //     stores while the compute waves are in the next tile's first chunk.
-// One barrier per chunk, one more per launch.
+// One barrier per chunk, one more per launch -- and one more per tile when a tile is ONE chunk (c_in == 64, no noise rows): the
+// stagers then drain tile t - 1 in the same phase in which the compute waves write tile t into the io tile, and barrier (B) orders
+// the two (conv2dbf.hip's (B)).
 #include <stdlib.h>
 
 #include <algorithm>
@@ -262,6 +264,7 @@ upsbf_kernel(const UbParams p) {
         for (int q = 0; q < n_q; ++q) {
             lds_barrier();                                    // (A) buffer q & 1 complete; the compute waves are done with buffer (q + 1) & 1
             if (cc_i == 0 && q > 0) out_store(tile0 + (ct_i - 1) * nslot);
+            if (ncht == 1) lds_barrier();                     // (B) the previous tile is out of the io tile (wave-uniform)
             if (q + 1 < n_q) x_write(q + 1, wc);
             adv(wt, wc);
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -354,7 +357,9 @@ upsbf_kernel(const UbParams p) {
             g0 += noise ? KS : NGC;
         }
         // ---- epilogue: interleaved into the io tile [channel][q r + ph] (the bias is the stagers': they know a row's channel) ------------
-        // (the stagers took the previous tile's outputs out of it behind this tile's first barrier A)
+        // (the stagers drain the previous tile's outputs in the phase after this tile's first barrier A: a tile of two or more chunks has
+        // passed a second A when it gets here, a tile of one chunk has not, and barrier B takes that A's place)
+        if (ncht == 1) lds_barrier();                         // (B)
 #pragma unroll
         for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
@@ -375,15 +380,16 @@ upsbf_kernel(const UbParams p) {
 // ---- host side -------------------------------------------------------------------------------------------------------------
 
 static int ub_mb(int rate, int c_out) {
-    const int rows = rate * c_out;
+    const int64_t rows = (int64_t)rate * c_out;
     return rows >= 256 ? 256 : rows >= 128 ? 128 : 64;
 }
 
+// exactly the shapes launch_upsbf has an instantiation for (its RVC_UB_CASE list): rate 2 at every MB, rates 8 / 10 / 12 at MB 128 / 256
 bool upsbf_supported(int c_in, int c_out, int rate, int ksize, int vk) {
     if (!(rate == 2 || rate == 8 || rate == 10 || rate == 12)) return false;
     if (c_in % UB_CK || c_in < UB_CK || c_out < 1 || ksize > 2 * rate || ksize < rate) return false;
     if (vk < 0 || vk >= UB_CK) return false;     // + the ones row
-    return rate <= ub_mb(rate, c_out);
+    return rate == 2 || ub_mb(rate, c_out) >= 128;
 }
 
 static void ub_dims(int c_in, int c_out, int rate, int vk, int *mb, int *n_mblk, int *ngt) {
@@ -500,8 +506,12 @@ using namespace rvc;
 
 extern "C" int rvc_upsample_bf16x3_weight_bytes(int c_in, int c_out, int rate, int ksize, int nc_k, int nc_stride, size_t *bytes) {
     if (!bytes) return fail("rvc_upsample_bf16x3_weight_bytes: null pointer");
+    if (nc_k < 0 || (nc_k > 0 && nc_stride < 1)) return fail("rvc_upsample_bf16x3_weight_bytes: bad noise conv (%d taps, stride %d)", nc_k, nc_stride);
     const int vk = upsbf_fold_noise(nc_k) ? (rate - 1) * nc_stride + nc_k : 0;
-    if (!upsbf_supported(c_in, c_out, rate, ksize, vk)) return fail("rvc_upsample_bf16x3_weight_bytes: unsupported shape");
+    if (!upsbf_supported(c_in, c_out, rate, ksize, vk))
+        return fail("rvc_upsample_bf16x3_weight_bytes: unsupported shape (%d -> %d channels, rate %d, kernel %d, %d noise rows): rate must be 2, "
+                    "8, 10 or 12 (8 / 10 / 12 with rate * c_out >= 128), c_in a multiple of 64, rate <= ksize <= 2 rate, "
+                    "(rate - 1) nc_stride + nc_k <= 63", c_in, c_out, rate, ksize, vk);
     *bytes = upsbf_weight_bytes(c_in, c_out, rate, vk);
     return 0;
 }

@@ -435,8 +435,10 @@ int rvc_conv1d_bf16w_forward(const float *x_dev, const void *u_dev, const float 
  * (channel, phase), two taps); the noise conv (one input channel, nc_k taps, stride nc_stride; nc_k = 0: none) enters as
  * (rate - 1) nc_stride + nc_k < 64 extra GEMM rows read straight from har_source [batch][har_len], plus a row of ones whose taps are the
  * bias (so pack_weight takes it: ups bias + noise-conv bias [c_out]); without a noise conv bias_dev is added on the way out.
- * rate in {2, 8, 10, 12}, c_in % 64 == 0; length_out = (length_in - 1) rate - 2 pad + ksize.  Every fp32 operand split exactly into
- * three bf16, six products, fp32 accumulate (csrc/upsbf.hip); persistent whole-CU workgroups. */
+ * Accepted shapes (weight_bytes and pack_weight refuse every other): rate in {2, 8, 10, 12}, and rate * c_out >= 128 for 8, 10 and 12;
+ * c_in a positive multiple of 64; c_out >= 1; rate <= ksize <= 2 rate; nc_k >= 0, and nc_stride >= 1 with
+ * (rate - 1) nc_stride + nc_k <= 63 when nc_k > 0.  length_out = (length_in - 1) rate - 2 pad + ksize.  Every fp32 operand split exactly
+ * into three bf16, six products, fp32 accumulate (csrc/upsbf.hip); persistent whole-CU workgroups. */
 int rvc_upsample_bf16x3_weight_bytes(int c_in, int c_out, int rate, int ksize, int nc_k, int nc_stride, size_t *bytes);
 int rvc_upsample_bf16x3_pack_weight(const float *up_w_host, const float *noise_w_host, const float *bias_host, int c_in, int c_out,
                                     int rate, int ksize, int nc_k, int nc_stride, void *u_dev, void *stream);

@@ -313,12 +313,13 @@ def test_decoder_T3198_stage_by_stage_vs_oracle(S, oracle_farm, case):
 @pytest.mark.parametrize("cfg", [2, 4, 5])
 def test_convert_batch_full_length_inflight2_equals_sequential(S, hubert, monkeypatch, cfg):
     """The benchmarked MODE at the benchmarked LENGTH, for every vocoder bench.py runs that way: four 30 s utterances through
-    convert_batch with THREE in flight (bench.py's default since round 6; rounds 2-5: two) against the same four converted one at a time -- cfg 2 (48 k NSF vocoder), cfg 4 (MRF vocoder,
-    bf16 weight storage: K3f with one-term taps next to K3y) and cfg 5 (RefineGAN, whose narrow layers still run wino_conv_kernel,
-    the kernel that profiles/r05_mfma_cohabitation.txt shows returning wrong words next to a co-resident bf16-matrix workgroup: here
-    it runs for 30 s beside the OTHER utterance's bf16 kernels, kept apart only by their whole-CU LDS request), 100 k index,
+    convert_batch with THREE in flight (bench.py's default since round 6; rounds 2-5: two, hence the name) against the same four
+    converted one at a time -- cfg 2 (48 k NSF vocoder), cfg 4 (MRF vocoder, bf16 weight storage: K3f with one-term taps next to K3y)
+    and cfg 5 (RefineGAN: since round 6 its narrow (conv, conv) pairs run K3f too, so wino_conv_kernel -- the fp32 kernel that
+    profiles/r05_mfma_cohabitation.txt shows returning wrong words next to a co-resident bf16-matrix workgroup -- is on no default path;
+    the bf16 matrix kernels of all three utterances share the chip, kept apart only by their whole-CU LDS request), 100 k index,
     index_rate 0.75.  The synthesizer's random draws are zeroed (RefineGAN: its 24 AdaIN noise tensors too) so that both runs are
-    deterministic; every kernel of one utterance then runs next to the other utterance's HuBERT / retrieval / vocoder kernels for
+    deterministic; every kernel of one utterance then runs next to the other utterances' HuBERT / retrieval / vocoder kernels for
     the whole 30 s, which the 3-6 s clips of test_convert_batch_inflight_equals_sequential do not give.  Gate 1e-5: the library
     GEMMs are not bit-stable run to run."""
     from rvc_amd.infer.infer import VoiceConverter

@@ -111,6 +111,10 @@ def test_conv1d_winograd_matches_float64(native, dev, c_in, c_out, k, dil, lengt
     # three taps (F(4,3), six points, winobf2.hip only): every dilation, ragged lengths, batch, one chunk, odd chunk count, full length
     (128, 128, 3, 1, 4096, 1), (128, 128, 3, 3, 4097, 1), (256, 256, 3, 5, 2051, 2), (128, 128, 3, 5, 31, 1), (256, 128, 3, 1, 777, 1),
     (16, 128, 3, 1, 3000, 1), (48, 128, 3, 3, 5000, 1), (256, 256, 3, 1, 50, 2), (128, 128, 3, 2, 9999, 1), (128, 128, 3, 1, 383760, 1),
+    # dilations 2 and 4 at 3, 7 and 11 taps: winobf2.hip (c_out % 128 == 0), then winobf.hip (64 output channels) at 7 and 11
+    (256, 128, 3, 2, 1237, 2), (128, 128, 3, 4, 2051, 1), (256, 256, 3, 4, 777, 2), (128, 128, 7, 2, 3001, 1), (64, 128, 7, 2, 999, 2),
+    (256, 256, 7, 4, 1003, 2), (128, 128, 7, 4, 513, 1), (128, 128, 11, 2, 1999, 2), (192, 128, 11, 2, 1537, 1), (128, 256, 11, 4, 2047, 1),
+    (128, 128, 11, 4, 4099, 2), (64, 64, 7, 2, 1001, 1), (64, 64, 7, 4, 2999, 2), (128, 64, 11, 2, 777, 2), (64, 64, 11, 4, 1537, 1),
 ])
 def test_conv1d_winograd_bf16x3_matches_float64(native, dev, c_in, c_out, k, dil, length, batch):
     """winobf.hip / winobf2.hip: the F(4,4) form of the 7- / 11-tap ResBlock convs and the F(4,3) form of the 3-tap ones at
@@ -150,6 +154,10 @@ def test_conv1d_winograd_bf16x3_matches_float64(native, dev, c_in, c_out, k, dil
     (64, 11, 3, 117, 1), (64, 7, 5, 50, 1),
     (128, 3, 1, 4096, 1), (128, 3, 3, 1237, 2), (128, 3, 5, 61, 1), (128, 7, 1, 2051, 1), (128, 7, 5, 777, 1),
     (32, 7, 3, 1535040, 1), (32, 11, 5, 1535040, 1), (64, 7, 1, 767520, 1), (64, 3, 5, 767520, 1), (128, 3, 3, 383760, 1),   # the benchmarked stage shapes
+    # dilations 2 and 4 (accepted, run by no decoder) at every accepted (channels, taps): ragged lengths, half of them at batch 2
+    (32, 3, 2, 1999, 1), (32, 3, 4, 1003, 2), (32, 7, 2, 2047, 2), (32, 7, 4, 3001, 1), (32, 11, 2, 777, 1), (32, 11, 4, 4099, 2),
+    (64, 3, 2, 1237, 2), (64, 3, 4, 2051, 1), (64, 7, 2, 999, 1), (64, 7, 4, 1537, 2), (64, 11, 2, 3003, 1), (64, 11, 4, 513, 2),
+    (128, 3, 2, 2051, 1), (128, 3, 4, 777, 2), (128, 7, 2, 1001, 2), (128, 7, 4, 2999, 1),
 ])
 def test_resblock_pair_bf16x3_matches_float64(native, dev, c, k, dil, length, batch):
     """resblock_bf.hip (K3f): one (dilated conv -> conv) pair of ResBlock.forward (residuals.py:75-86) in one launch, direct form on
@@ -194,6 +202,10 @@ def test_resblock_pair_bf16x3_matches_float64(native, dev, c, k, dil, length, ba
     (32, 11, 5, 31, 1), (32, 3, 1, 5, 1), (64, 3, 5, 777, 2), (64, 7, 1, 5003, 1), (64, 11, 1, 2051, 1), (64, 11, 5, 9999, 2),
     (64, 11, 3, 117, 1), (128, 3, 3, 1237, 2), (128, 7, 1, 2051, 1), (128, 7, 5, 777, 1), (128, 7, 3, 50, 1),
     (32, 11, 5, 1535040, 1), (64, 11, 3, 767520, 1), (128, 7, 5, 383760, 1),   # the cfg-4 stage shapes
+    # dilations 2 and 4 at every accepted (channels, taps)
+    (32, 3, 2, 2051, 2), (32, 3, 4, 999, 1), (32, 7, 2, 1237, 1), (32, 7, 4, 2047, 2), (32, 11, 2, 3001, 2), (32, 11, 4, 513, 1),
+    (64, 3, 2, 777, 1), (64, 3, 4, 4099, 2), (64, 7, 2, 2999, 2), (64, 7, 4, 1003, 1), (64, 11, 2, 1537, 1), (64, 11, 4, 2051, 2),
+    (128, 3, 2, 1001, 2), (128, 3, 4, 3003, 1), (128, 7, 2, 1999, 1), (128, 7, 4, 777, 2),
 ])
 def test_resblock_pair_bf16_taps_matches_float64(native, dev, c, k, dil, length, batch):
     """K3f with ONE-TERM taps (rvc_resblock_bf16w_*): BASELINE cfg 4's "alt ResBlock kernel path" -- the MRF layer
@@ -238,6 +250,9 @@ def test_resblock_pair_bf16_taps_matches_float64(native, dev, c, k, dil, length,
     (128, 11, 1, 4096, 1), (128, 11, 3, 4097, 1), (128, 11, 5, 777, 2), (128, 3, 1, 1000, 1), (128, 7, 5, 31, 1), (128, 11, 5, 63, 1),
     (256, 3, 1, 2051, 1), (256, 7, 3, 1237, 2), (256, 11, 5, 5003, 1), (256, 11, 1, 64, 1), (256, 7, 1, 65, 1), (256, 11, 3, 9999, 1),
     (128, 11, 5, 383760, 1), (256, 11, 3, 38376, 1), (256, 7, 5, 38376, 1),   # the cfg-4 stage shapes
+    # dilations 2 and 4 at every accepted (channels, taps)
+    (128, 3, 2, 2051, 2), (128, 3, 4, 999, 1), (128, 7, 2, 1237, 1), (128, 7, 4, 2047, 2), (128, 11, 2, 3001, 2), (128, 11, 4, 513, 1),
+    (256, 3, 2, 777, 1), (256, 3, 4, 1999, 2), (256, 7, 2, 2999, 2), (256, 7, 4, 1003, 1), (256, 11, 2, 1537, 1), (256, 11, 4, 2051, 2),
 ])
 def test_conv1d_bf16_taps_direct_matches_float64(native, dev, c, k, dil, length, batch):
     """K3d (convbf1.hip, rvc_conv1d_bf16w_*): one square conv of the MRF layer (hifigan_mrf.py:13-83 = residuals.py:75-86) with bf16-stored
@@ -319,6 +334,163 @@ def test_upsample_bf16x3_matches_float64(native, dev, c_in, c_out, rate, ksize, 
     print(f"upsample {c_in}->{c_out} x{rate} k{ksize} noise {nc_k}/{nc_stride} L {length} B {batch}: relative RMS error vs float64: bf16x3 {rel:.2e}, torch fp32 {rel_lib:.2e}")
     assert rel <= max(1.5 * rel_lib, 3e-7)
     assert torch.equal(native.upsample_bf16x3_forward(*args), got)
+
+
+def conv_transpose1d_dev(x, w, b=None, stride=1, padding=0, dtype=torch.float64):
+    """F.conv_transpose1d(x, w, b, stride, padding) evaluated on the device in `dtype` as one matrix product per tap (rocBLAS), each
+    scattered onto every stride-th output: in float64 the reference, in float32 torch's own fp32 arithmetic on the same sums (no
+    library convolution, so no per-shape kernel search).  Returns a tensor on the device."""
+    dev0 = torch.device("cuda:0")
+    xd, wd = x.to(dev0, dtype), w.to(dev0, dtype)
+    batch, c_in, length = xd.shape
+    _, c_out, k = wd.shape
+    full = (length - 1) * stride + k
+    y = torch.zeros(batch, c_out, full, dtype=dtype, device=dev0)
+    for t in range(k):
+        y[:, :, t: t + (length - 1) * stride + 1: stride] += torch.matmul(wd[:, :, t].t(), xd)
+    y = y[:, :, padding: full - padding]
+    if b is not None:
+        y += b.to(dev0, dtype)[None, :, None]
+    return y
+
+
+def noise_conv_dev(har, nw, stride, pad, l_out, dtype=torch.float64):
+    """F.conv1d(har[:, None], nw, stride=stride, padding=pad)[:, :, :l_out] with har zero outside [0, har_len) on both sides (what
+    K3u reads), on the device in `dtype`, one multiply-add per tap."""
+    dev0 = torch.device("cuda:0")
+    hd, wd = har.to(dev0, dtype), nw.to(dev0, dtype).reshape(nw.shape[0], -1)
+    k = wd.shape[1]
+    hp = F.pad(hd, (pad, max(0, (l_out - 1) * stride + k - pad - hd.shape[-1])))
+    y = torch.zeros(hd.shape[0], wd.shape[0], l_out, dtype=dtype, device=dev0)
+    for t in range(k):
+        y += wd[None, :, t, None] * hp[:, None, t: t + (l_out - 1) * stride + 1: stride]
+    return y
+
+
+def _ub_geometry(c_in, c_out, rate, nc_k, length, batch, cus):
+    """upsbf.hip's host arithmetic: (MB, m-blocks, slab bytes, chunks per tile, tiles, workgroups) of one K3u launch."""
+    rows = rate * c_out
+    mb = 256 if rows >= 256 else 128 if rows >= 128 else 64
+    n_mblk = -(-rows // mb)
+    n1 = 128 if mb == 64 else 64                                      # GEMM columns (input positions) per tile
+    ngt = c_in // 64 * 8 + (4 if nc_k else 0)
+    n_tiles = -(-(length + 1) // n1) * n_mblk * batch
+    per_xcd = -(-n_tiles // 8)
+    return mb, n_mblk, n_mblk * ngt * (mb // 32) * 3072, c_in // 64 + (1 if nc_k else 0), n_tiles, 8 * min(cus // 8, per_xcd)
+
+
+def _cu_count(dev):
+    return torch.cuda.get_device_properties(dev).multi_processor_count // 8 * 8
+
+
+def _wrong_samples(d, gate):
+    bad = d.abs() > gate
+    return f"{int(bad.sum())} samples beyond {gate:.2e} (max {d.abs().max().item():.3e}), first [batch, channel, t]: {bad.nonzero()[:8].tolist()}"
+
+
+def _upsample_case(native, dev, c_in, c_out, rate, ksize, nc_k, nc_stride, length, batch, *, seed, use_bias=True, nc_pad=None,
+                   har_len=None, label="upsample"):
+    """One K3u launch against float64 at test_upsample_bf16x3_matches_float64's gates; returns the launch geometry (_ub_geometry)."""
+    g = torch.Generator().manual_seed(seed)
+    pad = (ksize - rate) // 2
+    x = torch.randn(batch, c_in, length, generator=g)
+    w = torch.randn(c_in, c_out, ksize, generator=g) / (2 * c_in) ** 0.5
+    b = torch.randn(c_out, generator=g) if use_bias else None
+    l_out = (length - 1) * rate - 2 * pad + ksize
+    ref = conv_transpose1d_dev(F.leaky_relu(x.double(), 0.1), w, b, rate, pad)
+    lib = conv_transpose1d_dev(F.leaky_relu(x, 0.1), w, b, rate, pad, torch.float32)
+    har, nw = None, None
+    if nc_k:
+        nc_pad = max(0, (nc_k - nc_stride) // 2) if nc_pad is None else nc_pad
+        har = torch.randn(batch, l_out * nc_stride if har_len is None else har_len, generator=g)
+        nw = torch.randn(c_out, 1, nc_k, generator=g) * 0.3
+        ref += noise_conv_dev(har, nw, nc_stride, nc_pad, l_out)
+        lib += noise_conv_dev(har, nw, nc_stride, nc_pad, l_out, torch.float32)
+    assert ref.shape == (batch, c_out, l_out)
+    geo = _ub_geometry(c_in, c_out, rate, nc_k, length, batch, _cu_count(dev))
+    need = ctypes.c_size_t()
+    assert native._lib.rvc_upsample_bf16x3_weight_bytes(c_in, c_out, rate, ksize, nc_k, nc_stride, ctypes.byref(need)) == 0, native._lib.rvc_last_error()
+    assert need.value == geo[2], (need.value, geo)                   # the launch takes the (rate, MB) kernel this test counts
+    packed = native.upsample_bf16x3_pack_weight(w, nw, b, rate, nc_stride, dev)
+    args = (x.to(dev), har.to(dev) if har is not None else None, packed, c_out, rate, ksize, pad, nc_stride, nc_pad or 0, 0.1)
+    got = native.upsample_bf16x3_forward(*args)
+    assert got.shape == ref.shape
+    d = got.double() - ref
+    gate = 2e-5 * max(1.0, ref.abs().max().item())
+    assert d.abs().max().item() <= gate, _wrong_samples(d, gate)
+    ref_rms = ref.pow(2).mean().sqrt().item()
+    rel = d.pow(2).mean().sqrt().item() / ref_rms
+    rel_lib = (lib.double() - ref).pow(2).mean().sqrt().item() / ref_rms
+    print(f"{label} {c_in}->{c_out} x{rate} k{ksize} noise {nc_k}/{nc_stride} L {length} B {batch} (MB {geo[0]}, {geo[3]} chunk(s) per tile, "
+          f"{geo[4]} tiles on {geo[5]} workgroups): relative RMS error vs float64: bf16x3 {rel:.2e}, torch fp32 {rel_lib:.2e}")
+    assert rel <= max(1.5 * rel_lib, 3e-7)
+    assert torch.equal(native.upsample_bf16x3_forward(*args), got)
+    return geo
+
+
+@pytest.mark.parametrize("c_in,c_out,rate,ksize,nc_k,nc_stride,length,batch,use_bias", [
+    # ONE chunk per tile (c_in 64, no noise rows): barrier B orders the stagers' drain of tile t - 1 and the epilogue of tile t; every
+    # workgroup walks tens of tiles
+    (64, 32, 2, 4, 0, 1, 767520, 1, True), (64, 64, 2, 4, 0, 1, 100003, 1, True), (64, 16, 12, 24, 0, 1, 20001, 2, False),
+    # the instantiations no vocoder runs, ragged lengths: (12, 128); (10, 128) with 13 channels (130 rows: 2 live rows in the second
+    # m-block); (8, 128) at one and two m-blocks; (2, 256) at 128 and at 160 channels (two m-blocks, the second one partial)
+    (192, 20, 12, 20, 8, 2, 1999, 1, True), (256, 13, 10, 20, 0, 1, 2047, 2, True), (128, 16, 8, 16, 8, 4, 1537, 3, True),
+    (128, 31, 8, 13, 0, 1, 3001, 1, True), (128, 128, 2, 4, 4, 2, 3333, 2, True), (64, 160, 2, 4, 0, 1, 4097, 1, True),
+    # ksize == rate (the second tap is all zero); odd ksize - rate (pad rounds down)
+    (64, 64, 2, 2, 0, 1, 1001, 1, True), (128, 13, 10, 10, 4, 1, 517, 2, True), (128, 64, 2, 3, 0, 1, 2001, 1, True),
+    (128, 32, 8, 13, 2, 4, 999, 2, True),
+    # vk == 63: the row of ones that carries the bias is the last row of the noise chunk; with and without a bias
+    (128, 32, 8, 16, 7, 8, 1234, 2, True), (64, 16, 8, 16, 7, 8, 2001, 1, False),
+])
+def test_upsample_bf16x3_every_kernel_and_edge_matches_float64(native, dev, c_in, c_out, rate, ksize, nc_k, nc_stride, length, batch, use_bias):
+    """K3u at the shapes its ABI accepts beyond the decoder's stages: tiles of ONE input chunk, the (rate, MB) instantiations no vocoder
+    runs, partial m-blocks, an all-zero second tap, odd ksize - rate, the bias row as the last noise row -- against float64 at
+    test_upsample_bf16x3_matches_float64's gates (2e-5 of the largest value; relative RMS at torch fp32's level; bit-reproducible)."""
+    _upsample_case(native, dev, c_in, c_out, rate, ksize, nc_k, nc_stride, length, batch, seed=c_in * 31 + c_out * 7 + rate + ksize + length,
+                   use_bias=use_bias)
+
+
+def test_upsample_bf16x3_random_shape_sweep(native, dev):
+    """K3u on 36 seeded random shapes from the whole space rvc_upsample_bf16x3_weight_bytes accepts -- every (rate, MB) instantiation
+    four times, c_in 64-512, ksize rate..2 rate, noise rows on / off (nc_stride 1-8, nc_k up to vk = 63, random nc_pad and har_len), bias
+    on / off, batch 1-3, lengths from 1 -- at the gates of test_upsample_bf16x3_matches_float64.  Coverage is asserted: all nine
+    instantiations, one-chunk tiles, several chunks with folded noise rows, launches with more tiles than workgroups."""
+    rng = np.random.default_rng(20261016)
+    cus = _cu_count(dev)
+    inst = [(12, 256), (10, 256), (8, 256), (12, 128), (10, 128), (8, 128), (2, 256), (2, 128), (2, 64)]
+    seen, n_single, n_noise, n_walk = set(), 0, 0, 0
+    for it in range(36):
+        if it % 9 == 0:
+            order = rng.permutation(len(inst))
+        rate, mb = inst[order[it % 9]]
+        lo = 1 if mb == 64 else -(-mb // rate)                         # the c_out class in which rate * c_out picks this MB
+        hi = (2 * mb - 1) // rate if mb < 256 else 2 * lo + 8
+        c_out = int(rng.integers(lo, hi + 1))
+        c_in = 64 * int(rng.integers(1, 9))
+        ksize = int(rng.integers(rate, 2 * rate + 1))
+        noise = bool(rng.integers(0, 2))
+        batch = int(rng.integers(1, 4))
+        length = int(rng.integers(1, max(2, min(6000, 3_000_000 // (c_out * rate * batch), 2_000_000 // (c_in * batch)))))
+        if it % 6 == 1:
+            c_in, noise = 64, False                                    # one chunk per tile
+        if it % 8 == 3:                                                # more tiles than workgroups: each walks several
+            n_mblk = -(-rate * c_out // mb)
+            length = (128 if mb == 64 else 64) * (cus // (n_mblk * batch) + 1) + int(rng.integers(0, 4000))
+        nc_k, nc_stride, nc_pad, har_len = 0, 1, None, None
+        if noise:
+            nc_stride = int(rng.choice([s for s in (1, 2, 4, 8) if (rate - 1) * s <= 62]))
+            nc_k = int(rng.integers(1, 63 - (rate - 1) * nc_stride + 1))
+            nc_pad = int(rng.integers(0, nc_k + 1))
+            l_out = (length - 1) * rate - 2 * ((ksize - rate) // 2) + ksize
+            har_len = l_out * nc_stride + int(rng.integers(-nc_stride, nc_stride + 1))
+        geo = _upsample_case(native, dev, c_in, c_out, rate, ksize, nc_k, nc_stride, length, batch, seed=5000 + it,
+                             use_bias=bool(rng.integers(0, 2)), nc_pad=nc_pad, har_len=har_len, label=f"sweep {it}:")
+        assert geo[0] == mb
+        seen.add((rate, mb))
+        n_single += geo[3] == 1
+        n_noise += geo[3] >= 2 and nc_k > 0
+        n_walk += geo[4] > geo[5]
+    assert seen == set(inst) and n_single >= 3 and n_noise >= 3 and n_walk >= 3, (sorted(seen), n_single, n_noise, n_walk)
 
 
 @pytest.mark.parametrize("c,form", [(32, "three"), (64, "three"), (128, "three"), (32, "one"), (64, "one"), (128, "one"), (128, "direct"), (256, "direct")])

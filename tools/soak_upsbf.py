@@ -1,5 +1,6 @@
-"""K3u soak: random lengths / batches over every stage shape of the 48 / 40 / 32 k vocoders (and their noise convs) against
-F.conv_transpose1d + F.conv1d in float64; usage: python tools/soak_upsbf.py [seed]."""
+"""K3u soak: random lengths / batches over every stage shape of the 48 / 40 / 32 k vocoders (and their noise convs), the one-chunk
+tiles (c_in 64, no noise rows) and the (rate, MB) instantiations no vocoder runs, against F.conv_transpose1d + F.conv1d in float64;
+usage: python tools/soak_upsbf.py [seed]."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "codename-rvc-fork-3_amd"))
 import numpy as np, torch, torch.nn.functional as F
@@ -7,7 +8,9 @@ from rvc_amd import _native as N
 dev = torch.device("cuda:0")
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 3)
 shapes = [(512, 256, 12, 24, 0, 1), (256, 128, 10, 20, 8, 4), (128, 64, 2, 4, 4, 2), (64, 32, 2, 4, 1, 1), (512, 256, 10, 16, 0, 1),
-          (256, 128, 10, 16, 8, 4), (256, 128, 8, 16, 8, 4), (128, 64, 2, 4, 0, 1), (256, 128, 10, 20, 0, 1), (512, 256, 12, 24, 0, 1)]
+          (256, 128, 10, 16, 8, 4), (256, 128, 8, 16, 8, 4), (128, 64, 2, 4, 0, 1), (256, 128, 10, 20, 0, 1), (512, 256, 12, 24, 0, 1),
+          (64, 32, 2, 4, 0, 1), (64, 64, 2, 4, 0, 1), (64, 16, 12, 24, 0, 1),                       # one chunk per tile (barrier B)
+          (192, 20, 12, 20, 8, 2), (256, 13, 10, 20, 0, 1), (128, 16, 8, 16, 8, 4), (128, 128, 2, 4, 4, 2), (64, 160, 2, 4, 0, 1)]   # (12 / 10 / 8, 128), (2, 256)
 worst = 0.0
 for it in range(120):
     c_in, c_out, rate, ksize, nc_k, nc_stride = shapes[int(rng.integers(0, len(shapes)))]
