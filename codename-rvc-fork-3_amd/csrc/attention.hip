@@ -606,8 +606,15 @@ static int choose_splits(int64_t n_frames, int n_heads, int batch) {
 
 using namespace rvc;
 
+// the one shape predicate of the size query and the forward: the kernels are instantiated for these two head widths only
+static bool attention_shape_ok(int batch, int64_t n_frames, int n_heads, int head_dim) {
+    return batch > 0 && n_heads > 0 && n_frames >= 0 && (head_dim == 64 || head_dim == 96);
+}
+
 extern "C" int rvc_attention_workspace_bytes(int batch, int64_t n_frames, int n_heads, int head_dim, size_t *bytes) {
-    if (!bytes || batch <= 0 || n_heads <= 0 || n_frames < 0 || head_dim <= 0) return fail("rvc_attention_workspace_bytes: bad argument");
+    if (!bytes) return fail("rvc_attention_workspace_bytes: null pointer");
+    if (head_dim != 64 && head_dim != 96) return fail("rvc_attention_workspace_bytes: head_dim must be 64 or 96, got %d", head_dim);
+    if (!attention_shape_ok(batch, n_frames, n_heads, head_dim)) return fail("rvc_attention_workspace_bytes: bad shape");
     const int splits = choose_splits(n_frames, n_heads, batch);
     const size_t rows = (size_t)batch * n_heads * splits * (size_t)n_frames;
     *bytes = splits == 1 ? 256 : align_up(rows * head_dim * sizeof(float), 256) + align_up(rows * 2 * sizeof(float), 256);
@@ -638,7 +645,7 @@ extern "C" int rvc_attention_qkv_f32(const float *qkv_dev, const float *emb_rel_
     if (!qkv_dev || !out_dev) return fail("rvc_attention_qkv_f32: null pointer");
     if (head_dim != 64 && head_dim != 96) return fail("rvc_attention_qkv_f32: head_dim must be 64 or 96, got %d", head_dim);
     if ((emb_rel_k_dev == nullptr) != (emb_rel_v_dev == nullptr)) return fail("rvc_attention_qkv_f32: emb_rel_k and emb_rel_v go together");
-    if (batch <= 0 || n_heads <= 0 || n_frames < 0) return fail("rvc_attention_qkv_f32: bad shape");
+    if (!attention_shape_ok(batch, n_frames, n_heads, head_dim)) return fail("rvc_attention_qkv_f32: bad shape");
     if (n_frames == 0) return 0;
     if ((int64_t)n_frames * 3 * n_heads * head_dim * 4 >= ((int64_t)1 << 32))
         return fail("rvc_attention_qkv_f32: one batch element of %lld frames exceeds the 4 GB the kernel addresses", (long long)n_frames);

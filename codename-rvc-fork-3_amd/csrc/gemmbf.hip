@@ -412,7 +412,9 @@ extern "C" int rvc_conv1d_bf16x3(const float *x_dev, const void *a_dev, const fl
     if (c_out % GBF_BM || (!one_channel && c_in % 16) || k < 1 || stride < 1 || padding < 0) return fail("rvc_conv1d_bf16x3: c_out must be a multiple of 128, c_in of 16");
     if ((int64_t)c_out * c_in * k * 6 >= ((int64_t)1 << 31)) return fail("rvc_conv1d_bf16x3: weight slab exceeds 2 GiB");
     if (act < 0 || act > 1) return fail("rvc_conv1d_bf16x3: act must be 0 (none) or 1 (gelu)");
-    const int64_t l_out = (l_in + 2 * padding - k) / stride + 1;
+    // an input shorter than one window has NO output: C division truncates toward zero, so (l_in + 2 padding - k) / stride + 1 is 1
+    // for a deficit below `stride` (l_in 2, k 3, stride 2), and the kernel would store one column the caller never allocated
+    const int64_t l_out = l_in + 2 * padding >= k ? (l_in + 2 * padding - k) / stride + 1 : 0;
     if (l_out <= 0 || batch <= 0) return 0;
     GemmBfParams p;
     p.a = a_dev; p.x = x_dev; p.y = y_dev; p.bias = bias_dev;

@@ -71,9 +71,12 @@ hubert_conv0_stats_kernel(const float *__restrict__ wav, int64_t n_frames, int s
     }
 }
 
-// one thread per channel: the chunks' sums in a fixed order -> mean, 1 / sqrt(var + eps) (biased variance, like torch's group_norm)
+// one thread per channel: the chunks' sums in a fixed order -> mean, 1 / sqrt(var + eps) (biased variance, like torch's group_norm).
+// The mean leaves as TWO floats, hi + lo: rounded to one, every deviation carries up to half an ulp of |mean|, which is the largest
+// error of the layer wherever the deviations are small against the mean (a two-frame clip: 1.5e-5 against torch fp32's 3.7e-6; a
+// quiet clip on a DC offset).  hi and 1 / std go to stats[], lo into this channel's own slot of chunk 0's sums, which are spent.
 __global__ void __launch_bounds__(256)
-hubert_conv0_finish_kernel(const double *__restrict__ part, int C, int64_t n_frames, float eps, float *__restrict__ stats) {
+hubert_conv0_finish_kernel(double *__restrict__ part, int C, int64_t n_frames, float eps, float *__restrict__ stats) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     double sum = 0.0, sq = 0.0;
@@ -81,19 +84,21 @@ hubert_conv0_finish_kernel(const double *__restrict__ part, int C, int64_t n_fra
     const double mean = sum / (double)n_frames;
     double var = sq / (double)n_frames - mean * mean;
     var = var > 0.0 ? var : 0.0;
-    stats[2 * c] = (float)mean;
+    const float mean_hi = (float)mean;
+    stats[2 * c] = mean_hi;
     stats[2 * c + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    part[(int64_t)c * 2] = mean - (double)mean_hi;
 }
 
 // block = 32 frames x C channels; thread (frame f = tid / 8, channel group cg = tid % 8) -> channels 64 j + 8 cg + 0..7, j = 0 .. C / 64 - 1
 template <int TAPS>
 __global__ void __launch_bounds__(256)
 hubert_conv0_apply_kernel(const float *__restrict__ wav, int64_t n_frames, int stride, const float *__restrict__ w,
-                          const float *__restrict__ stats, const float *__restrict__ gamma, const float *__restrict__ beta,
-                          unsigned char *__restrict__ ys, int64_t n_pad, int C) {
+                          const float *__restrict__ stats, const double *__restrict__ mean_lo, const float *__restrict__ gamma,
+                          const float *__restrict__ beta, unsigned char *__restrict__ ys, int64_t n_pad, int C) {
     extern __shared__ __attribute__((aligned(16))) float hf_smem[];
     float *const wt = hf_smem;                 // [TAPS][C]
-    float *const tab = hf_smem + TAPS * C;     // [4][C]: mean, rstd, gamma, beta
+    float *const tab = hf_smem + TAPS * C;     // [5][C]: mean (hi), rstd, gamma, beta, mean (lo)
     const int tid = threadIdx.x;
     for (int i = tid; i < TAPS * C; i += 256) {
         const int c = i / TAPS, k = i - c * TAPS;
@@ -104,6 +109,7 @@ hubert_conv0_apply_kernel(const float *__restrict__ wav, int64_t n_frames, int s
         tab[C + c] = stats[2 * c + 1];
         tab[2 * C + c] = gamma ? gamma[c] : 1.f;
         tab[3 * C + c] = beta ? beta[c] : 0.f;
+        tab[4 * C + c] = (float)mean_lo[(int64_t)c * 2];
     }
     __syncthreads();
     const int64_t t = (int64_t)blockIdx.x * 32 + (tid >> 3);
@@ -126,7 +132,7 @@ hubert_conv0_apply_kernel(const float *__restrict__ wav, int64_t n_frames, int s
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = c0 + e;
-            const float n = (o[e] - tab[c]) * tab[C + c] * tab[2 * C + c] + tab[3 * C + c];
+            const float n = ((o[e] - tab[c]) - tab[4 * C + c]) * tab[C + c] * tab[2 * C + c] + tab[3 * C + c];
             o[e] = 0.5f * n * (1.f + erff(n * 0.70710678118654752f));
         }
         hf_f32x2 v[4] = {{o[0], o[1]}, {o[2], o[3]}, {o[4], o[5]}, {o[6], o[7]}};
@@ -148,8 +154,13 @@ hubert_conv0_apply_kernel(const float *__restrict__ wav, int64_t n_frames, int s
 
 using namespace rvc;
 
+// the one shape predicate of the size query and the forward: the apply kernel walks 64-channel groups and keeps (taps + 5) x channels
+// floats in LDS (61 440 bytes at 1024 channels)
+static bool hubert_conv0_shape_ok(int channels) { return channels > 0 && channels % 64 == 0 && channels <= 1024; }
+
 extern "C" int rvc_hubert_conv0_workspace_bytes(int channels, size_t *bytes) {
-    if (!bytes || channels <= 0) return fail("rvc_hubert_conv0_workspace_bytes: bad argument");
+    if (!bytes || !hubert_conv0_shape_ok(channels))
+        return fail("rvc_hubert_conv0_workspace_bytes: channels must be a multiple of 64 in [64, 1024], got %d", channels);
     *bytes = (size_t)channels * 2 * sizeof(float) + (size_t)HF_CHUNKS * channels * 2 * sizeof(double);
     return 0;
 }
@@ -159,12 +170,13 @@ extern "C" int rvc_hubert_conv0_frames_bf16x3(const float *wav_dev, int64_t n_sa
                                               size_t workspace_bytes, void *ys_dev, int64_t n_frames_padded, void *stream) {
     if (!wav_dev || !w_dev || !workspace_dev || !ys_dev) return fail("rvc_hubert_conv0_frames_bf16x3: null pointer");
     if (taps != 10) return fail("rvc_hubert_conv0_frames_bf16x3: built for HuBERT's 10-tap first layer, got %d taps", taps);
-    if (channels % 64 || channels <= 0 || channels > 1024 || stride < 1 || !(eps >= 0.f)) return fail("rvc_hubert_conv0_frames_bf16x3: bad argument");
+    if (!hubert_conv0_shape_ok(channels)) return fail("rvc_hubert_conv0_frames_bf16x3: channels must be a multiple of 64 in [64, 1024], got %d", channels);
+    if (stride < 1 || !(eps >= 0.f)) return fail("rvc_hubert_conv0_frames_bf16x3: bad argument");
     const int64_t n_frames = n_samples >= taps ? (n_samples - taps) / stride + 1 : 0;
     if (n_frames <= 0) return fail("rvc_hubert_conv0_frames_bf16x3: the clip is shorter than one window");
     if (n_frames_padded < n_frames) return fail("rvc_hubert_conv0_frames_bf16x3: n_frames_padded < frames");
     size_t need = 0;
-    (void)rvc_hubert_conv0_workspace_bytes(channels, &need);
+    if (rvc_hubert_conv0_workspace_bytes(channels, &need)) return 1;
     if (workspace_bytes < need) return fail("rvc_hubert_conv0_frames_bf16x3: workspace too small (%zu < %zu)", workspace_bytes, need);
     double *part = reinterpret_cast<double *>(workspace_dev);                                  // (first: 8-byte aligned)
     float *stats = reinterpret_cast<float *>(part + (size_t)HF_CHUNKS * channels * 2);
@@ -174,9 +186,9 @@ extern "C" int rvc_hubert_conv0_frames_bf16x3(const float *wav_dev, int64_t n_sa
     RVC_LAUNCH_CHECK();
     hipLaunchKernelGGL(hubert_conv0_finish_kernel, dim3((unsigned)ceil_div(channels, 256)), dim3(256), 0, st, part, channels, n_frames, eps, stats);
     RVC_LAUNCH_CHECK();
-    const size_t lds = (size_t)(taps + 4) * channels * sizeof(float);
+    const size_t lds = (size_t)(taps + 5) * channels * sizeof(float);
     hipLaunchKernelGGL(hubert_conv0_apply_kernel<10>, dim3((unsigned)ceil_div(n_frames, 32)), dim3(256), lds, st, wav_dev, n_frames, stride,
-                       w_dev, stats, gamma_dev, beta_dev, reinterpret_cast<unsigned char *>(ys_dev), n_frames_padded, channels);
+                       w_dev, stats, part, gamma_dev, beta_dev, reinterpret_cast<unsigned char *>(ys_dev), n_frames_padded, channels);
     RVC_LAUNCH_CHECK();
     return 0;
 }

@@ -278,6 +278,15 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float *__restrict
     }
 }
 
+// The row mean as ONE rounded fp32 value.  Left to the compiler, `v - sum * (1 / M)` contracts into an fma on the unrounded product:
+// with 768 features (1 / 768 is inexact) a row of equal values then has deviations of 3e-8 |v| instead of 0, and LayerNorm returns
+// beta + 1e-5 |v| gamma (eps 1e-5) where the answer is beta.
+__device__ __forceinline__ float ln_row_mean(float sum, float inv_m) {
+    float mean = sum * inv_m;
+    asm volatile("" : "+v"(mean));   // an opaque use: the rounded product is a value of its own, nothing contracts across it
+    return mean;
+}
+
 // one wave per row: v = sum of the K parts + bias + residual; LayerNorm over the row (two passes in registers, fp32 like
 // torch.nn.functional.layer_norm); fp32 out and the three planes
 template <int PER_LANE>   // M = 64 * PER_LANE, PER_LANE a multiple of 4
@@ -303,7 +312,7 @@ __global__ void __launch_bounds__(256) ln_reduce_kernel(const float *__restrict_
     for (int q = 0; q < Q; ++q) sum += (v[q].x + v[q].y) + (v[q].z + v[q].w);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float mean = sum * (1.f / M);
+    const float mean = ln_row_mean(sum, 1.f / M);
     float sq = 0.f;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {

@@ -778,7 +778,9 @@ def linear_bf16x3_presplit(xs: torch.Tensor, a_packed: torch.Tensor, bias, n_row
     if m in (0, 3):
         y = out if out is not None else torch.empty((n_rows, out_features), dtype=torch.float32, device=xs.device)
     elif m == 1:
-        y = out if out is not None else planes_empty(n_rows, out_features, xs.device)
+        # (the output planes share n_rows_padded with the input planes: sized by xs, not by n_rows, or a caller whose planes are
+        # longer than rows_padded(n_rows) would have planes 1 and 2 written past the end)
+        y = out if out is not None else torch.empty((3, n_pad, out_features), dtype=torch.bfloat16, device=xs.device)
     else:
         y = out if out is not None else torch.empty((k_parts, n_rows, out_features), dtype=torch.float32, device=xs.device)
     _check(_lib.rvc_linear_bf16x3_presplit(xs.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
@@ -867,8 +869,10 @@ def conv1d_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, c_out: int, k: 
     """nn.Conv1d(c_in, c_out, k, stride, padding) + activation for x [batch, c_in, L] (fp32, HBM, contiguous)."""
     x = _dev_f32(x, "x")
     b, c_in, l_in = x.shape
-    l_out = (l_in + 2 * padding - k) // stride + 1
+    l_out = max((l_in + 2 * padding - k) // stride + 1, 0)
     y = torch.empty((b, c_out, l_out), dtype=torch.float32, device=x.device)
+    if y.numel() == 0:   # an input shorter than one window: an empty result, and no call with an empty tensor's NULL pointer
+        return y
     _check(_lib.rvc_conv1d_bf16x3(x.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), b,
                                   c_in, c_out, l_in, k, stride, padding, {"none": 0, "gelu": 1}[act], _stream()), "rvc_conv1d_bf16x3")
     return y

@@ -173,7 +173,8 @@ int rvc_bigru_forward(const float *gi_dev, const float *whhT_dev, const float *b
  * head_dim 64 without relative terms (HuBERT) runs both GEMMs on the bf16 matrix cores instead, every fp32 operand split exactly into
  * three bf16 (six products, fp32 accumulate: fp32-level results, max abs error vs float64 ~4e-6 at 1599 frames); its 8-wave workgroups
  * request the CU's whole LDS like every kernel of this library that issues bf16 matrix instructions.
- * workspace_dev: rvc_attention_workspace_bytes() bytes (partial results when the keys are split; the K / V fragment slab of the bf16 form). */
+ * workspace_dev: rvc_attention_workspace_bytes() bytes (partial results when the keys are split; the K / V fragment slab of the bf16 form).
+ * The size query accepts exactly what the forward accepts: batch > 0, n_heads > 0, n_frames >= 0, head_dim 64 or 96. */
 int rvc_attention_workspace_bytes(int batch, int64_t n_frames, int n_heads, int head_dim, size_t *bytes);
 int rvc_attention_qkv_f32(const float *qkv_dev, const float *emb_rel_k_dev, const float *emb_rel_v_dev, float *out_dev,
                           int batch, int64_t n_frames, int n_heads, int head_dim, float scale, void *workspace_dev,
@@ -462,6 +463,7 @@ int rvc_resblock_bf16x3_set_enabled(int enabled);
  * Weights: rvc_gemm_bf16x3_weight_bytes() bytes filled by rvc_gemm_bf16x3_pack_weight from the [out][in] (linear, conv_taps = 1) or
  * [C_out][C_in][taps] (conv, conv_taps = taps, k_total = taps * C_in) host tensor.  out / C_out a multiple of 128, in / C_in of 16. * rvc_conv1d_bf16x3 also takes c_in = 1 with k <= 16, no padding, batch 1 (HuBERT's first layer: Conv1d(1, 512, 10, stride 5)); the
  * kernel reads nothing beyond x[l_in - 1].  rvc_gemm_bf16x3_weight_bytes / _pack_weight pad such a weight to one k16 step.
+ * rvc_conv1d_bf16x3 writes l_out = (l_in + 2 padding - k) / stride + 1 columns per channel, and NOTHING when l_in + 2 padding < k.
  */
 int rvc_gemm_bf16x3_weight_bytes(int m, int k_total, size_t *bytes);
 int rvc_gemm_bf16x3_pack_weight(const float *w_host, int m, int k_total, int conv_taps, void *a_dev, void *stream);
@@ -502,8 +504,9 @@ int rvc_bias_residual_layernorm_bf16x3(const float *parts_dev, int n_parts, cons
  * and needs no im2col, no transposes and no fp32 copy of the 196 MB first-layer output.
  * rvc_hubert_conv0_frames_bf16x3 (csrc/hubert_front.hip): layer 0 from the 16 kHz samples; the conv is evaluated twice (float64
  *   statistics over the clip, then normalise + GELU + split) instead of being stored.  w_dev [channels][taps] fp32, taps = 10,
- *   channels a multiple of 64; workspace of rvc_hubert_conv0_workspace_bytes(channels); ys_dev planes with
- *   n_frames_padded >= (n_samples - taps) / stride + 1 rows.
+ *   channels a multiple of 64, at most 1024 (the size query refuses every other count, like the forward); workspace of
+ *   rvc_hubert_conv0_workspace_bytes(channels) = channels * 136 bytes; ys_dev planes with n_frames_padded >= (n_samples - taps) /
+ *   stride + 1 rows.
  * rvc_conv1d_frames_bf16x3 (csrc/linbf.hip): xs_dev planes [3][n_frames_in_padded][channels]; a_dev = rvc_gemm_bf16x3_pack_weight's
  *   slab of the [out][taps * channels] matrix W[o][k * channels + c] = conv.weight[o][c][k]; output frames (n_frames_in - taps) /
  *   stride + 1; modes 0 / 1 / 3 of rvc_linear_bf16x3_presplit (ys_dev planes [3][n_frames_out_padded][out_channels] or y_dev

@@ -1,7 +1,9 @@
-"""The shape contract of the vocoder's bf16 matrix-core kernels at the C ABI (include/rvc_amd.h): every `rvc_*_weight_bytes` size query
-accepts EXACTLY the shapes its header comment documents -- the shapes its forward has a kernel for -- and every refusal says why in
-rvc_last_error().  pack_weight asks the same query first, so what it accepts is pinned with it.  Size queries only, no device: a clean
-CPU checkout catches a predicate that drifts (K3u's once accepted rates 8 / 10 / 12 at 64-row tiles, which have no kernel)."""
+"""The shape contract of the bf16 matrix-core kernels at the C ABI (include/rvc_amd.h) -- the vocoder's convs (K3u / K3f / K3d / K3y) and the
+HuBERT side (K11 GEMM slab, K14 positional conv, K7 attention workspace, K13 first-layer workspace): every `rvc_*_weight_bytes` /
+`_workspace_bytes` size query accepts EXACTLY the shapes its header comment documents -- the shapes its forward has a kernel for -- and
+every refusal says why in rvc_last_error().  pack_weight asks the same query first, so what it accepts is pinned with it.  Size queries
+only, no device: a clean CPU checkout catches a predicate that drifts (K3u's once accepted rates 8 / 10 / 12 at 64-row tiles, which
+have no kernel; the attention and K13 workspace queries once accepted any positive head_dim / channel count)."""
 import ctypes
 import itertools
 
@@ -23,8 +25,9 @@ def _plant_other_error(lib):
     assert b"k must be 8" in lib.rvc_last_error()
 
 
-def _check_grid(lib, name, grid, documented):
-    """Call `name`(*args, &bytes) over `grid`; accepted <=> documented(*args); a refusal leaves a message naming `name`."""
+def _check_grid(lib, name, grid, documented, value=None):
+    """Call `name`(*args, &bytes) over `grid`; accepted <=> documented(*args); a refusal leaves a message naming `name`; where `value` is
+    given, an accepted call returns exactly value(*args) bytes."""
     fn = getattr(lib, name)
     need = ctypes.c_size_t()
     n_yes = n_no = 0
@@ -37,6 +40,8 @@ def _check_grid(lib, name, grid, documented):
         assert (rc == 0) == want, (name, args, "accepted" if rc == 0 else "refused", lib.rvc_last_error())
         if want:
             assert need.value > 0, (name, args)
+            if value is not None:
+                assert need.value == value(*args), (name, args, need.value, value(*args))
             n_yes += 1
         else:
             msg = lib.rvc_last_error()
@@ -128,3 +133,81 @@ def test_conv1d_winobf_weight_bytes_accepts_exactly_the_documented_shapes(lib):
     grid = [(c_out, c_in, k) for k in range(0, 14) for c_out in c_outs for c_in in c_ins]
     n_yes, n_no = _check_grid(lib, "rvc_conv1d_winobf_weight_bytes", grid, _winobf_documented)
     assert n_yes >= 1000 and n_no >= n_yes, (n_yes, n_no)
+
+
+# ---- K11: rvc_gemm_bf16x3_weight_bytes(m, k) ------------------------------------------------------------------------------------------
+def test_gemm_bf16x3_weight_bytes_accepts_exactly_the_documented_shapes(lib):
+    """m a positive multiple of 128; k a positive multiple of 16, or 1 .. 15 (the one-input-channel conv, padded to one k16 step)."""
+    ms = sorted(set(range(-128, 4097, 64)) | {-1, 1, 127, 129, 255, 4095})
+    ks = list(range(-1, 70)) + sorted(set(range(64, 3101, 16)) | {767, 769, 3071, 3073, 3100})
+    grid = list(itertools.product(ms, ks))
+    n_yes, n_no = _check_grid(lib, "rvc_gemm_bf16x3_weight_bytes", grid, lambda m, k: m > 0 and m % 128 == 0 and k > 0 and (k % 16 == 0 or k < 16),
+                              value=lambda m, k: m * max(k, 16) * 6)
+    assert n_yes >= 5000 and n_no >= n_yes, (n_yes, n_no)
+
+
+# ---- K14: rvc_posconv_bf16x3_weight_bytes(d, groups, taps) ---------------------------------------------------------------------------
+def _posconv_documented(d, groups, taps):
+    return groups > 0 and d > 0 and d % groups == 0 and d // groups in (48, 64) and 1 <= taps <= 128
+
+
+def test_posconv_weight_bytes_accepts_exactly_the_documented_shapes(lib):
+    ds = sorted(set(range(-48, 1100, 16)) | {1, 47, 49, 63, 65, 767, 769, 1023, 1025})
+    grid = [(d, groups, taps) for d in ds for groups in (-1, 0, 1, 2, 3, 8, 12, 15, 16, 17, 24)
+            for taps in (-1, 0, 1, 2, 5, 64, 127, 128, 129, 256)]
+    n_yes, n_no = _check_grid(lib, "rvc_posconv_bf16x3_weight_bytes", grid, _posconv_documented,
+                              value=lambda d, groups, taps: groups * taps * (d // groups // 16) * 6144)
+    assert n_yes >= 80 and n_no >= 10 * n_yes, (n_yes, n_no)
+    w = (ctypes.c_float * (96 * 96 * 2))()
+    slab = ctypes.create_string_buffer(1 << 16)        # a host buffer: a refused pack copies nothing into it
+    _plant_other_error(lib)
+    assert lib.rvc_posconv_bf16x3_pack_weight(w, 96, 1, 2, slab, None) != 0            # 96 channels per group
+    assert lib.rvc_last_error().startswith(b"rvc_posconv_bf16x3_weight_bytes: ") and slab.raw == bytes(len(slab))
+
+
+# ---- K7 / K7b: rvc_attention_workspace_bytes(batch, n_frames, n_heads, head_dim) ----------------------------------------------------
+def test_attention_workspace_bytes_accepts_exactly_the_documented_shapes(lib):
+    """The forward has kernels for head_dim 64 and 96 only (before: the query accepted any positive head_dim, and the forward then
+    refused the shape the caller had sized a workspace for)."""
+    grid = list(itertools.product((-1, 0, 1, 2, 3), (-1, 0, 1, 31, 32, 33, 257, 1599, 4799), (-1, 0, 1, 2, 12),
+                                  list(range(-1, 130)) + [192, 256]))
+    n_yes, n_no = _check_grid(lib, "rvc_attention_workspace_bytes", grid,
+                              lambda b, t, h, d: b > 0 and h > 0 and t >= 0 and d in (64, 96))
+    assert n_yes == 3 * 8 * 3 * 2 and n_no >= 10 * n_yes, (n_yes, n_no)
+
+
+# ---- K13: rvc_hubert_conv0_workspace_bytes(channels) ------------------------------------------------------------------------------
+def test_hubert_conv0_workspace_bytes_accepts_exactly_the_documented_shapes(lib):
+    """channels a multiple of 64 in [64, 1024], what the forward takes (before: any positive count); 8 chunks of (sum, sum of squares) in
+    float64 plus (mean, rstd) in fp32 per channel."""
+    grid = [(c,) for c in range(-64, 2200)]
+    n_yes, n_no = _check_grid(lib, "rvc_hubert_conv0_workspace_bytes", grid, lambda c: c % 64 == 0 and 0 < c <= 1024,
+                              value=lambda c: c * (8 + 8 * 16))
+    assert n_yes == 16, n_yes
+
+
+def test_attention_workspace_bytes_follows_the_split_rule_the_gpu_tests_mirror(lib):
+    """test_front_kernels_gpu._att_plan mirrors the split choice of csrc/attention.hip to assert which branches its sweep reaches; the
+    size query exposes that choice (the partial results scale with the split count), so the mirror is held to the library here, on
+    the CPU, over 1-3 utterances x 1-12 heads x 0-4800 frames.  The rule never picks 8 splits: 7 is the most a test can reach."""
+    from test_front_kernels_gpu import _att_plan
+    align = lambda n: -(-n // 256) * 256
+    need = ctypes.c_size_t()
+    seen = set()
+    for batch in (1, 2, 3):
+        for heads in (1, 2, 3, 5, 8, 12):
+            for frames in list(range(0, 700)) + list(range(700, 4801, 37)):
+                for hd in (64, 96):
+                    _, s7, _, _ = _att_plan(batch, frames, heads, hd, True)          # K7's rule (the REL form always takes K7)
+                    rows = batch * heads * s7 * frames
+                    want = 256 if s7 == 1 else align(rows * hd * 4) + align(rows * 8)
+                    if hd == 64:
+                        kernel, sb, _, _ = _att_plan(batch, frames, heads, 64, False)
+                        assert kernel == "K7b"
+                        rows = 0 if sb == 1 else batch * heads * sb * frames
+                        want = max(want, align(rows * 256) + align(rows * 8) + align(batch * heads * -(-frames // 32) * 24576))
+                        seen.add(sb)
+                    seen.add(s7)
+                    assert lib.rvc_attention_workspace_bytes(batch, frames, heads, hd, ctypes.byref(need)) == 0
+                    assert need.value == want, (batch, frames, heads, hd, need.value, want)
+    assert seen == {1, 2, 3, 4, 5, 6, 7}, sorted(seen)

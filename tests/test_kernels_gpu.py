@@ -1412,6 +1412,22 @@ def test_bigru_timeout_is_recomputed_not_poisoned(native, dev):
 
 
 # ---- K7 attention ------------------------------------------------------------------------------------
+def _attention_vs_torch_fp32(qkv, got, heads, hd, emb_k, emb_v, label):
+    """The gate every other bf16x3 test of this file has, for the attention kernels: against a float64 evaluation of the same formula
+    ON THE SAME fp32 operands (on the device), relative RMS at most 2 x and max abs at most 4 x what torch's fp32 eager evaluation
+    leaves -- six fp32 accumulations per product where fp32 has one are at most sqrt(6) = 2.4 x in rounding walk, the hardware exp2
+    adds 1 ulp.  A bf16x3 kernel that drops one of its six products errs at 2^-16 of the operands: inside the 2e-5 outer bound of the
+    callers, far outside this one.  Floored where torch's own error is below the noise of tiny cases (test_front_kernels_gpu.py)."""
+    from test_front_kernels_gpu import ATT_REL_FLOOR, _attention_ref, _maxabs, _rel
+    ref = _attention_ref(qkv.double(), heads, hd, emb_k.double() if emb_k is not None else None, emb_v.double() if emb_v is not None else None)
+    lib = _attention_ref(qkv, heads, hd, emb_k, emb_v)
+    got = got.to(qkv.device)
+    r, rl, e, el = _rel(got, ref), _rel(lib, ref), _maxabs(got, ref), _maxabs(lib, ref)
+    print(f"{label}: rel rms {r:.2e} (torch fp32 {rl:.2e}, ratio {r / max(rl, 1e-30):.2f}), max abs {e:.2e} (torch {el:.2e}, ratio {e / max(el, 1e-30):.2f})")
+    assert r <= 2.0 * max(rl, ATT_REL_FLOOR), (r, rl)
+    assert e <= 4.0 * max(el, ATT_REL_FLOOR * max(1.0, ref.abs().max().item())), (e, el)
+
+
 @pytest.mark.parametrize("batch,frames,heads,hd", [(1, 1, 12, 64), (1, 31, 2, 64), (2, 97, 12, 64), (1, 1599, 12, 64),
                                                    (1, 64, 3, 64), (1, 200, 2, 96), (2, 333, 2, 96),
                                                    (1, 256, 1, 64), (1, 257, 5, 64), (3, 500, 4, 64), (1, 4799, 12, 64)])
@@ -1419,7 +1435,9 @@ def test_attention_matches_float64_softmax(native, dev, batch, frames, heads, hd
     """softmax(q k^T / sqrt(d)) v against a float64 evaluation of the same formula (what transformers' HubertAttention
     computes, modeling_hubert.py eager path), on the fused-projection layout [B, T, 3, H, d]; key splits included.  Head dim 64
     runs K7b (attention_bf_kernel: bf16x3 products, 8-wave workgroups of 256 queries -- whole / partial / single workgroups per
-    head, 1-8 key splits, a 45 s utterance's 4799 frames), head dim 96 K7."""
+    head, 1-7 key splits, a 45 s utterance's 4799 frames), head dim 96 K7.  (1, 257, 5, 64) and (2, 333, 2, 96) end in key splits that
+    own no tile (test_front_kernels_gpu.py pins that and sweeps the rest of the space).  Two gates: 2e-5 of the largest value as the
+    outer bound, and _attention_vs_torch_fp32 -- at most 2 x (relative RMS) / 4 x (max abs) torch fp32's own error on the same operands."""
     torch.manual_seed(frames)
     qkv = torch.randn(batch, frames, 3 * heads * hd) * 1.5
     got = native.attention_qkv(qkv.to(dev), heads, hd ** -0.5).cpu()
@@ -1428,12 +1446,14 @@ def test_attention_matches_float64_softmax(native, dev, batch, frames, heads, hd
     assert got.shape == ref.shape and torch.isfinite(got).all()
     # tolerance: fp32 dot products of 64 terms and a 2^x hardware exp (1 ulp) under a row sum -> a few 1e-6 relative
     assert (got.double() - ref).abs().max().item() <= 2e-5 * max(1.0, ref.abs().max().item())
+    _attention_vs_torch_fp32(qkv.to(dev), got, heads, hd, None, None, f"attention [{batch} x {frames} x {heads} x {hd}]")
 
 
 @pytest.mark.parametrize("batch,frames,heads,hd", [(1, 5, 2, 96), (1, 64, 2, 96), (2, 171, 2, 96), (1, 3198, 2, 96), (1, 100, 3, 64)])
 def test_relative_attention_matches_oracle(native, dev, batch, frames, heads, hd):
     """TextEncoder attention with window-10 relative-position terms against the oracle's restatement of
-    attentions.py:101-180 (pad/reshape formulation, float64)."""
+    attentions.py:101-180 (pad/reshape formulation, float64; its q / k / v projections are float64 too, hence the 3e-5), and, on the
+    fp32 qkv the kernel is given, against a float64 evaluation of rvc_amd.h's formula relative to torch fp32 (_attention_vs_torch_fp32)."""
     from oracle import rvc_oracle as O
     torch.manual_seed(frames + hd)
     c = heads * hd
@@ -1450,6 +1470,8 @@ def test_relative_attention_matches_oracle(native, dev, batch, frames, heads, hd
                                w["a.emb_rel_v"][0].contiguous().to(dev)).cpu().transpose(1, 2)
     assert got.shape == ref.shape and torch.isfinite(got).all()
     assert (got.double() - ref).abs().max().item() <= 3e-5 * max(1.0, ref.abs().max().item())
+    _attention_vs_torch_fp32(qkv.to(dev), got.transpose(1, 2), heads, hd, w["a.emb_rel_k"][0].contiguous().to(dev), w["a.emb_rel_v"][0].contiguous().to(dev),
+                             f"relative attention [{batch} x {frames} x {heads} x {hd}]")
 
 
 # ---- K8 conv epilogue --------------------------------------------------------------------------------
