@@ -323,22 +323,18 @@ struct AttBfParams {
     float scale_log2e;
 };
 constexpr int ABF_TILE_BYTES = 24 * 1024, ABF_NW = 8;
-typedef __bf16 abf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 abf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float abf_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned abf_u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3))) *abf_lptr_t;
 
 // eight fp32 values -> their three bf16 "digits" (exact: v = d0 + d1 + d2 up to 2^-24 relative), packed as fragment registers
-__device__ __forceinline__ void abf_split8(const float (&v)[8], abf_u32x4 (&out)[3]) {
-    abf_f32x2 r[4] = {abf_f32x2{v[0], v[1]}, abf_f32x2{v[2], v[3]}, abf_f32x2{v[4], v[5]}, abf_f32x2{v[6], v[7]}};
+__device__ __forceinline__ void abf_split8(const float (&v)[8], u32x4 (&out)[3]) {
+    f32x2 r[4] = {f32x2{v[0], v[1]}, f32x2{v[2], v[3]}, f32x2{v[4], v[5]}, f32x2{v[6], v[7]}};
 #pragma unroll
     for (int level = 0; level < 3; ++level)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector(r[q], abf_bf16x2));
+            const unsigned w = split_word(r[q]);
             out[level][q] = w;
-            if (level < 2) r[q] = r[q] - abf_f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+            if (level < 2) r[q] = r[q] - f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
         }
 }
 
@@ -368,11 +364,11 @@ __global__ void __launch_bounds__(512) attention_pack_kv_kernel(const float *__r
         }
         piece0 = 12 + (db * 2 + ks) * 3;
     }
-    abf_u32x4 d[3];
+    u32x4 d[3];
     abf_split8(v, d);
     unsigned char *dst = frag + ((int64_t)blockIdx.y * n_tiles + tile) * ABF_TILE_BYTES + lane * 16;
 #pragma unroll
-    for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<abf_u32x4 *>(dst + (piece0 + sp) * 1024) = d[sp];
+    for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<u32x4 *>(dst + (piece0 + sp) * 1024) = d[sp];
 }
 
 // DBG (ablation build; wrong results): 1 no matrix instructions, 2 no exponentials / splits, 4 no fragment reads from LDS, 8 no DMA in the loop,
@@ -405,7 +401,7 @@ attention_bf_kernel(const AttBfParams p) {
     // 52 -> 59 us; the softmax's vector work pinned piece by piece behind the next tile's score products with sched_barrier, 59.
     // Ablation of this form: no matrix instructions 24 us of 52-59, fixed cost of a workgroup ~10, exp + splits ~10, LDS reads ~10.)
     const int64_t n_frag = (int64_t)gridDim.y * nt_all * ABF_TILE_BYTES;
-    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)p.frag, 0, (int)n_frag, 0x00020000);
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc((void *)p.frag, 0, (int)n_frag, RSRC_RAW32);
     const int bh_base = (int)((int64_t)blockIdx.y * nt_all) * ABF_TILE_BYTES;
     constexpr int HALF = ABF_TILE_BYTES / 2;
     // pieces 0..11: K of tile tk -> K ring slot kslot; pieces 12..23: V of tile tv -> V ring slot vslot (a tile < 0: nothing)
@@ -427,7 +423,7 @@ attention_bf_kernel(const AttBfParams p) {
         dma(t_begin + 1 < t_end ? t_begin + 1 : -1, 1, -1, 0);
     }
     // query fragments: lane (query j, half h) holds Q[q0 + j][16 ks + 8 h + e], pre-scaled by scale * log2(e), as three bf16 digits
-    abf_u32x4 qf[4][3];
+    u32x4 qf[4][3];
     {
         const int64_t q = q0 + j < T ? q0 + j : T - 1;
         const float *ptr = p.qkv + b * T * rs + (int64_t)head * 64 + q * rs + 8 * h;
@@ -446,11 +442,11 @@ attention_bf_kernel(const AttBfParams p) {
         for (int r = 0; r < 16; ++r) sc[r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            abf_bf16x8 kf[3];
+            bf16x8 kf[3];
 #pragma unroll
-            for (int sp = 0; sp < 3; ++sp) if (!(DBG & 4)) kf[sp] = __builtin_bit_cast(abf_bf16x8, *reinterpret_cast<const abf_u32x4 *>(kk + (ks * 3 + sp) * 1024));
+            for (int sp = 0; sp < 3; ++sp) if (!(DBG & 4)) kf[sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(kk + (ks * 3 + sp) * 1024));
 #pragma unroll
-            for (int i = 0; i < 6; ++i) if (!(DBG & 1)) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ia6[i]], __builtin_bit_cast(abf_bf16x8, qf[ks][ib6[i]]), sc, 0, 0, 0);
+            for (int i = 0; i < 6; ++i) if (!(DBG & 1)) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ia6[i]], __builtin_bit_cast(bf16x8, qf[ks][ib6[i]]), sc, 0, 0, 0);
         }
         return sc;
     };
@@ -504,7 +500,7 @@ attention_bf_kernel(const AttBfParams p) {
                 }
                 l += psum;
                 // ---- O^T[dim][query] += V^T P^T: the lane's own probabilities are the "B" operand, 8 keys per k-step and half ----
-                abf_u32x4 pf[2][3];
+                u32x4 pf[2][3];
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const float v[8] = {sc[8 * ks], sc[8 * ks + 1], sc[8 * ks + 2], sc[8 * ks + 3], sc[8 * ks + 4], sc[8 * ks + 5], sc[8 * ks + 6], sc[8 * ks + 7]};
@@ -515,13 +511,13 @@ attention_bf_kernel(const AttBfParams p) {
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                     for (int db = 0; db < 2; ++db) {
-                        abf_bf16x8 vf[3];
+                        bf16x8 vf[3];
 #pragma unroll
                         for (int sp = 0; sp < 3; ++sp)
-                            if (!(DBG & 4)) vf[sp] = __builtin_bit_cast(abf_bf16x8, *reinterpret_cast<const abf_u32x4 *>(vv + ((db * 2 + ks) * 3 + sp) * 1024));
+                            if (!(DBG & 4)) vf[sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(vv + ((db * 2 + ks) * 3 + sp) * 1024));
 #pragma unroll
                         for (int i = 0; i < 6; ++i)
-                            if (!(DBG & 1)) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ia6[i]], __builtin_bit_cast(abf_bf16x8, pf[ks][ib6[i]]), o[db], 0, 0, 0);
+                            if (!(DBG & 1)) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ia6[i]], __builtin_bit_cast(bf16x8, pf[ks][ib6[i]]), o[db], 0, 0, 0);
                     }
                 s_cur = s_next;
             }
@@ -649,7 +645,7 @@ extern "C" int rvc_attention_qkv_f32(const float *qkv_dev, const float *emb_rel_
     if (n_frames == 0) return 0;
     if ((int64_t)n_frames * 3 * n_heads * head_dim * 4 >= ((int64_t)1 << 32))
         return fail("rvc_attention_qkv_f32: one batch element of %lld frames exceeds the 4 GB the kernel addresses", (long long)n_frames);
-    if (head_dim == 64 && !emb_rel_k_dev && att_bf_enabled() && (int64_t)batch * n_heads * ceil_div(n_frames, 32) * ABF_TILE_BYTES < ((int64_t)1 << 31)) {
+    if (head_dim == 64 && !emb_rel_k_dev && att_bf_enabled() && fits_2gib((int64_t)batch * n_heads * ceil_div(n_frames, 32), ABF_TILE_BYTES)) {
         // K7b: split K / V into fragments, then one CU-owning workgroup per (256 queries, head, key split)
         size_t off_ml = 0, off_frag = 0;
         const size_t need = att_bf_workspace(batch, n_frames, n_heads, &off_ml, &off_frag);

@@ -9,6 +9,7 @@
 
 #include <string>
 
+#include "bf16x3.h"
 #include "rvc_amd.h"
 
 namespace rvc {
@@ -57,6 +58,27 @@ int reserve_whole_cu(const void *kernel, const char *what);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// compute units of the device that was current at the first call (256 when the query fails)
+int cu_count();
+
+// The grid of a persistent kernel that owns its CU and walks n_tiles tiles: XCD x (workgroup id & 7) owns the contiguous range
+// [x per_xcd, (x + 1) per_xcd) and its workgroups walk it side by side; at most one workgroup per CU, none without a tile.
+struct PersistentGrid {
+    int per_xcd;       // tiles per XCD
+    unsigned blocks;   // workgroups: 8 x min(CUs per XCD, per_xcd)
+};
+static inline PersistentGrid persistent_grid(int64_t n_tiles) {
+    const int per_xcd = (int)ceil_div(n_tiles, 8), cus_per_xcd = cu_count() / 8;
+    return {per_xcd, 8u * (unsigned)(cus_per_xcd < per_xcd ? cus_per_xcd : per_xcd)};
+}
+
+// raw buffer descriptors address 2 GiB (bf16x3.h: BUF_OOB lies beyond it): true when `elems` elements fit below
+static inline bool fits_2gib(int64_t elems, int elem_bytes) { return elems * elem_bytes < ((int64_t)1 << 31); }
+
+// the tail of every rvc_*_pack_weight: a packed host staging buffer -> the caller's device slab, complete on return (the staging
+// buffer dies with the call); sets the error "<fn>: <hip error>" and returns non-zero on failure
+int upload_packed(const char *fn, const void *host, size_t bytes, void *dev, void *stream);
 
 // ---- device-side MFMA typedefs ---------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));

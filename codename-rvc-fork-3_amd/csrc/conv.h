@@ -111,6 +111,16 @@ static inline uint16_t bf16_rne(float f) {
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
+// v -> out[0 .. n_terms): the first n_terms bf16 of v's exact split (bf16x3.h's split3 on the host); n_terms = 1 is plain rounding
+static inline void bf16_split_host(float v, int n_terms, uint16_t *out) {
+    for (int s = 0; s < n_terms; ++s) {
+        out[s] = bf16_rne(v);
+        const uint32_t bits = (uint32_t)out[s] << 16;
+        float f;
+        memcpy(&f, &bits, 4);
+        v -= f;   // exact in fp32
+    }
+}
 
 // fast (Winograd F(4,3), grouped) form of the 3 / 7 / 11-tap dilated convs (wino.hip): y = out_scale * (conv(act(x)) + bias + res + accin)
 bool wino_enabled();   // RVC_WINO != 0 (conv.hip)

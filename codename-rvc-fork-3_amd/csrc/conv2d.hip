@@ -47,7 +47,6 @@ constexpr int c2_patch_max(int bn, int pad) {
     }
     return best;
 }
-constexpr int C2_RSRC = 0x00020000;
 typedef void __attribute__((address_space(3))) *c2_lptr_t;
 
 template <int WM, int WN, int NT, int TAPS>
@@ -83,8 +82,8 @@ __global__ void __launch_bounds__(256) conv2d_mfma_kernel(const Conv2dParams p) 
     const int sp = blockIdx.z;
     const int HW = H * W;
     const float *px = p.x + (int64_t)b * c_in * HW;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, c_in * HW * 4, C2_RSRC);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, TAPS * c_in * p.m_pad * 4, C2_RSRC);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, c_in * HW * 4, RSRC_RAW32);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.w, 0, TAPS * c_in * p.m_pad * 4, RSRC_RAW32);
 
     // ---- staging plan: position pos = tid + j * 256 of the patch, the same for each of the chunk's 8 channels ------------
     unsigned goff[NJ];    // byte offset of the sample inside a channel plane
@@ -325,7 +324,7 @@ int launch_conv2d(const float *x, const float *w, const float *bias, const float
     if (taps != 9 && taps != 1) return fail("conv2d: %d taps unsupported (3x3 or 1x1)", taps);
     if (c_in % C2_CIC) return fail("conv2d: c_in %d is not a multiple of %d", c_in, C2_CIC);
     if (W < 4 || W > 128 || (W & (W - 1))) return fail("conv2d: row length %d unsupported (a power of two in 4..128)", W);
-    if ((int64_t)c_in * H * W >= ((int64_t)1 << 29) || (int64_t)c_out * H * W >= ((int64_t)1 << 29))
+    if (!fits_2gib((int64_t)c_in * H * W, 4) || !fits_2gib((int64_t)c_out * H * W, 4))
         return fail("conv2d: a %d x %d x %d map exceeds the kernel's 32-bit addressing", c_in > c_out ? c_in : c_out, H, W);
     if (batch <= 0 || H <= 0) return 0;
     Conv2dParams p;
@@ -364,10 +363,7 @@ extern "C" int rvc_conv2d_pack_weight(const float *w_host, int c_out, int c_in, 
     for (int co = 0; co < c_out; ++co)
         for (int ci = 0; ci < c_in; ++ci)
             for (int t = 0; t < taps; ++t) packed[((size_t)t * c_in + ci) * m_pad + co] = w_host[((size_t)co * c_in + ci) * taps + t];
-    hipError_t e = hipMemcpyAsync(w_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_conv2d_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_conv2d_pack_weight", packed.data(), packed.size() * sizeof(float), w_dev, stream);
 }
 
 extern "C" int rvc_conv2d_packed_floats(int c_out, int c_in, int kh, int kw, size_t *out) {

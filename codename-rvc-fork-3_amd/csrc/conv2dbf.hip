@@ -29,14 +29,7 @@
 
 namespace rvc {
 
-typedef __bf16 c2b_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c2b_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float c2b_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned c2b_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int C2B_NTH = 512;
-constexpr int C2B_RSRC = 0x00020000;
-constexpr unsigned C2B_OOB = 0x80000000u;   // beyond every tensor this kernel takes: loads return 0
 constexpr int C2B_CK = 16;                  // input channels per chunk = one 16-deep k step per tap
 constexpr int C2B_ROWB = 112;               // [split 3][channel 16] bf16 + 16 bytes
 constexpr int C2B_TAPS = 9;
@@ -85,28 +78,10 @@ struct C2bGeom {
     static_assert(LDS_BYTES <= 163840, "LDS budget");
 };
 
-__device__ __forceinline__ float c2b_sub_np(float a, float b) {   // plain fp32 VALU next to another wave's matrix instructions
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a, b) -> three words of two bf16 each whose sums are a and b exactly
-__device__ __forceinline__ void c2b_split3(float a, float b, unsigned w[3]) {
-#pragma unroll
-    for (int level = 0; level < 3; ++level) {
-        const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(c2b_f32x2{a, b}, c2b_bf16x2));
-        w[level] = ww;
-        if (level < 2) {
-            a = c2b_sub_np(a, __uint_as_float(ww << 16));
-            b = c2b_sub_np(b, __uint_as_float(ww & 0xffff0000u));
-        }
-    }
-}
-
 // offset of a buffer operation that may have to be a no-op: a select, never a branch
 __device__ __forceinline__ unsigned c2b_sel(bool ok, unsigned off) {
     unsigned r;
-    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(C2B_OOB), "v"(off), "s"((unsigned long long)__builtin_amdgcn_ballot_w64(ok)));
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(BUF_OOB), "v"(off), "s"((unsigned long long)__builtin_amdgcn_ballot_w64(ok)));
     return r;
 }
 
@@ -158,7 +133,7 @@ conv2dbf_kernel(const C2bParams p) {
     };
 
     // both patch buffers start as zeros (the padding columns stay that way)
-    for (int o = tid * 16; o < 2 * GM::X_BYTES; o += C2B_NTH * 16) *reinterpret_cast<c2b_u32x4 *>(xs + o) = c2b_u32x4{0u, 0u, 0u, 0u};
+    for (int o = tid * 16; o < 2 * GM::X_BYTES; o += C2B_NTH * 16) *reinterpret_cast<u32x4 *>(xs + o) = u32x4{0u, 0u, 0u, 0u};
     lds_barrier();
 
     // DBG & 64 (ablation build): wave 0 and wave 4 write cycle-counter stamps to `partial` (unsplit launches): [block][role 2][64]
@@ -202,7 +177,7 @@ conv2dbf_kernel(const C2bParams p) {
             int b, pxt, mblk;
             decode(k, b, pxt, mblk);
             const int t0 = pxt * th;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (valid ? (int64_t)b * p.c_in * HW : 0)), 0, num_bytes, C2B_RSRC);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (valid ? (int64_t)b * p.c_in * HW : 0)), 0, num_bytes, RSRC_RAW32);
             const int ch0 = (c_begin + c) * C2B_CK;
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -221,10 +196,10 @@ conv2dbf_kernel(const C2bParams p) {
                 for (int hf = 0; hf < 2; ++hf) {
                     unsigned w[4][3];
 #pragma unroll
-                    for (int e2 = 0; e2 < 4; ++e2) c2b_split3(xr[j][hf * 8 + 2 * e2], xr[j][hf * 8 + 2 * e2 + 1], w[e2]);
+                    for (int e2 = 0; e2 < 4; ++e2) split3_np(xr[j][hf * 8 + 2 * e2], xr[j][hf * 8 + 2 * e2 + 1], w[e2]);
 #pragma unroll
                     for (int s = 0; s < 3; ++s)
-                        *reinterpret_cast<c2b_u32x4 *>(xb + ldsoff[j] + s * 32 + hf * 16) = c2b_u32x4{w[0][s], w[1][s], w[2][s], w[3][s]};
+                        *reinterpret_cast<u32x4 *>(xb + ldsoff[j] + s * 32 + hf * 16) = u32x4{w[0][s], w[1][s], w[2][s], w[3][s]};
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -242,12 +217,12 @@ conv2dbf_kernel(const C2bParams p) {
             const int co = mblk * GM::BM + ps * RPP + orow, pix = pxt * th * W + ocol;
             return c2b_sel((int)valid & (int)(co < p.c_out) & (int)(pix < HW), (unsigned)(co * HW + pix) * 4u);
         };
-        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)(has_bias ? p.bias : p.x), 0, p.c_out * 4, C2B_RSRC);
+        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void *)(has_bias ? p.bias : p.x), 0, p.c_out * 4, RSRC_RAW32);
         auto epi_issue = [&](int k, bool valid) __attribute__((always_inline)) {
             int b, pxt, mblk;
             decode(k, b, pxt, mblk);
             const bool vr = (int)valid & (int)has_res;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(vr ? p.res + (int64_t)b * p.c_out * HW : p.x), 0, out_bytes, C2B_RSRC);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(vr ? p.res + (int64_t)b * p.c_out * HW : p.x), 0, out_bytes, RSRC_RAW32);
 #pragma unroll
             for (int ps = 0; ps < PASSES; ++ps)
                 rres[ps] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)out_offset(vr, mblk, pxt, ps), 0, 0));
@@ -261,14 +236,14 @@ conv2dbf_kernel(const C2bParams p) {
             int b, pxt, mblk;
             decode(k, b, pxt, mblk);
             float *const dst = !valid ? p.y : (whole ? p.y + (int64_t)b * p.c_out * HW : p.partial + ((int64_t)((int)blockIdx.y * p.batch + b) * p.c_out) * HW);
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)dst, 0, out_bytes, C2B_RSRC);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)dst, 0, out_bytes, RSRC_RAW32);
 #pragma unroll
             for (int ps = 0; ps < PASSES; ++ps) {
                 f32x4 v = *reinterpret_cast<const f32x4 *>(io + (ps * RPP + orow) * BN + ocol);
                 v += rbias[ps];
                 if (relu) v = f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
                 v += rres[ps];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(c2b_u32x4, v), rs, (int)out_offset(valid, mblk, pxt, ps), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (int)out_offset(valid, mblk, pxt, ps), 0, 0);
             }
         };
         // Per phase, behind barrier A(i) (item i's rows are complete in buffer i & 1, the compute waves are done with the other one, and
@@ -311,19 +286,19 @@ conv2dbf_kernel(const C2bParams p) {
         xl[cb] = (prw * PC + pcl) * ROWB + half * 16;
     }
     const int rowsh1 = PC * ROWB;
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)p.u_bytes, C2B_RSRC);
-    c2b_bf16x8 fa[PA][3];
-    c2b_bf16x8 fb[2][2][3];
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)p.u_bytes, RSRC_RAW32);
+    bf16x8 fa[PA][3];
+    bf16x8 fb[2][2][3];
     f32x16 acc[2];
     // tap fragments of group (item base, tap): three splits
     auto load_a = [&](int slot, unsigned vo, int base, int tap) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < 3; ++s)
-            fa[slot][s] = __builtin_bit_cast(c2b_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, (int)vo + s * 1024, base + tap * C2B_GROUP, 0));
+            fa[slot][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, (int)vo + s * 1024, base + tap * C2B_GROUP, 0));
     };
     auto load_b1 = [&](int buf, const unsigned char *src, int tap, int cb, int s) __attribute__((always_inline)) {
         const int dh = tap / 3, dw = tap - 3 * dh;
-        fb[buf][cb][s] = __builtin_bit_cast(c2b_bf16x8, *reinterpret_cast<const c2b_u32x4 *>(src + xl[cb] + dh * rowsh1 + dw * ROWB + s * 32));
+        fb[buf][cb][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(src + xl[cb] + dh * rowsh1 + dw * ROWB + s * 32));
     };
     auto item_base = [&](int mblk, int c) __attribute__((always_inline)) -> int {
         return (((mblk * MW + mw) * p.n_chunks_total + c_begin + c) * TAPS) * C2B_GROUP;
@@ -348,7 +323,7 @@ conv2dbf_kernel(const C2bParams p) {
         int bnx = b, pxtn = pxt, mblkn = mblk;
         if (cn == 0 && i + 1 < n_items) decode(kn, bnx, pxtn, mblkn);
         const int base_next = item_base(mblkn, cn);
-        const unsigned vo_next = i + 1 < n_items ? vo_lane : C2B_OOB;
+        const unsigned vo_next = i + 1 < n_items ? vo_lane : BUF_OOB;
         if (c == 0) {
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb)
@@ -417,8 +392,8 @@ bool conv2dbf_supported(int c_in, int c_out, int H, int W, int taps) {
     const int mw = c2b_mw(c_out);
     if (!mw || W > 64 * (4 / mw)) return false;
     const int m_pad = (c_out + 31) / 32 * 32;
-    if ((int64_t)c_in * H * W >= ((int64_t)1 << 29) || (int64_t)c_out * H * W >= ((int64_t)1 << 29)) return false;
-    return conv2dbf_weight_bytes(c_out, c_in) < ((size_t)1 << 31) && m_pad <= 4096;
+    if (!fits_2gib((int64_t)c_in * H * W, 4) || !fits_2gib((int64_t)c_out * H * W, 4)) return false;
+    return fits_2gib((int64_t)conv2dbf_weight_bytes(c_out, c_in), 1) && m_pad <= 4096;
 }
 
 size_t conv2dbf_weight_bytes(int c_out, int c_in) { return (size_t)((c_out + 31) / 32) * (c_in / C2B_CK) * C2B_TAPS * C2B_GROUP; }
@@ -435,16 +410,10 @@ void conv2dbf_pack_host(const float *w, int c_out, int c_in, std::vector<uint16_
                     for (int e = 0; e < 8; ++e) {
                         const int co = 32 * rb + (lane & 31), ci = C2B_CK * ch + 8 * (lane >> 5) + e;
                         if (co >= c_out) continue;
-                        float r = w[((size_t)co * c_in + ci) * C2B_TAPS + tap];
                         const size_t group = ((size_t)rb * NC + ch) * C2B_TAPS + tap;
-                        for (int s = 0; s < 3; ++s) {
-                            const uint16_t h = bf16_rne(r);
-                            const uint32_t bits = (uint32_t)h << 16;
-                            float f;
-                            memcpy(&f, &bits, 4);
-                            r -= f;                          // exact in fp32
-                            (*out)[(group * 3 + s) * 512 + lane * 8 + e] = h;
-                        }
+                        uint16_t h[3];
+                        bf16_split_host(w[((size_t)co * c_in + ci) * C2B_TAPS + tap], 3, h);
+                        for (int s = 0; s < 3; ++s) (*out)[(group * 3 + s) * 512 + lane * 8 + e] = h[s];
                     }
 }
 
@@ -458,15 +427,6 @@ static bool c2b_xcd_ranges() {
     return on != 0;
 }
 
-static int c2b_cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
-}
-
 // units (pixel tiles x channel blocks x batch), and how many ways K is split so that about one workgroup per CU runs
 static void c2b_plan(int batch, int c_in, int c_out, int H, int W, int *units, int *split, int *n_px_tiles, int *n_mblk) {
     const int mw = c2b_mw(c_out), bn = 64 * (4 / mw), th = bn / W;
@@ -474,7 +434,7 @@ static void c2b_plan(int batch, int c_in, int c_out, int H, int W, int *units, i
     *n_px_tiles = (int)ceil_div(H, th);
     *n_mblk = m_pad / (32 * mw);
     *units = batch * *n_px_tiles * *n_mblk;
-    const int nct = c_in / C2B_CK, cus = c2b_cu_count();
+    const int nct = c_in / C2B_CK, cus = cu_count();
     int s = 1;
     while (s * 2 <= 8 && *units * s * 2 <= cus && nct % (s * 2) == 0 && nct / (s * 2) >= 2) s *= 2;
     *split = s;
@@ -536,7 +496,7 @@ int launch_conv2dbf(const float *x, const void *u, const float *bias, const floa
 #ifdef RVC_ABLATE
     if (knob("RVC_C2B_DEBUG", 0) == 64 && p.split == 1) p.partial = ws;   // stamps (tools/stamp_conv2dbf.py hands over a workspace)
 #endif
-    const int cus = c2b_cu_count();
+    const int cus = cu_count();
     const int rounds = (int)ceil_div(p.n_units, cus);
     int grid_x = (int)ceil_div(p.n_units, rounds);            // every workgroup walks `rounds` units (the last ones one fewer)
     if (rounds > 1 && p.split == 1 && c2b_xcd_ranges()) {
@@ -572,10 +532,7 @@ extern "C" int rvc_conv2d_bf16x3_pack_weight(const float *w_host, int c_out, int
     if (rvc_conv2d_bf16x3_weight_bytes(c_out, c_in, kh, kw, &bytes)) return 1;
     std::vector<uint16_t> u;
     conv2dbf_pack_host(w_host, c_out, c_in, &u);
-    hipError_t e = hipMemcpyAsync(u_dev, u.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_conv2d_bf16x3_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_conv2d_bf16x3_pack_weight", u.data(), bytes, u_dev, stream);
 }
 
 extern "C" int rvc_conv2d_bf16x3_workspace_bytes(int batch, int c_in, int c_out, int height, int width, size_t *out) {

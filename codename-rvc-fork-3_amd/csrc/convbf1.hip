@@ -18,7 +18,7 @@
 //   * the compute waves issue no memory operation but their tap-fragment loads (L2); outputs leave through an LDS tile
 //     [channel][column] that the stagers drain with 16-byte row stores, adding residual / running sum / scale on the way
 //     (resblock_bf.hip's division of labour: a wave's memory operations retire in order).
-// One barrier per 64-channel chunk, two more per tile.
+// One barrier per 64-channel chunk, one more per launch.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -30,15 +30,7 @@
 
 namespace rvc {
 
-typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float cb_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned cb_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned cb_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CB1_NTH = 512;
-constexpr int CB1_RSRC_FLAGS = 0x00020000;
-constexpr unsigned CB1_OOB = 0x80000000u;   // beyond every tensor this kernel takes: loads return 0, stores are dropped
 constexpr int CB1_CK = 64;                  // input channels per chunk
 constexpr int CB1_N1 = 64;                  // output columns per tile
 
@@ -54,35 +46,6 @@ struct Cb1Params {
     float slope = 1.f, out_scale = 1.f;
     int tiles_per_row = 0, n_tiles = 0, per_xcd = 0;
 };
-
-// plain (unpacked) fp32 VALU next to another wave's matrix instructions (resblock_bf.hip: packed fp32 there costs ~100 cycles each)
-__device__ __forceinline__ float cb_sub_np(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float cb_add_np(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float cb_mul_np(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a, b) -> three words of two bf16 each whose sums are a and b exactly
-__device__ __forceinline__ void cb_split3_np(float a, float b, unsigned w[3]) {
-#pragma unroll
-    for (int level = 0; level < 3; ++level) {
-        const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(cb_f32x2{a, b}, cb_bf16x2));
-        w[level] = ww;
-        if (level < 2) {
-            a = cb_sub_np(a, __uint_as_float(ww << 16));
-            b = cb_sub_np(b, __uint_as_float(ww & 0xffff0000u));
-        }
-    }
-}
 
 template <int KW, int C>
 struct Cb1Geom {
@@ -149,7 +112,7 @@ convbf1_kernel(const Cb1Params p) {
             const int tl = tile0 + (q / NCH) * nslot, ch0 = (q % NCH) * CK;
             const int bb = tl / p.tiles_per_row;
             const int xt0 = (tl - bb * p.tiles_per_row) * N1 - H * d;                       // time of row 0
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * C * L), 0, num_bytes, CB1_RSRC_FLAGS);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
             const unsigned Lu = (unsigned)L;
             int sw_o = sw;
             asm volatile("" : "+s"(sw_o));                    // the per-item scalars are recomputed, not hoisted and spilled
@@ -162,7 +125,7 @@ convbf1_kernel(const Cb1Params p) {
                 const unsigned base = (unsigned)(ch0 + 4 * qd) * L4 + tg * 4u;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : CB1_OOB), 0, 0));
+                    xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : BUF_OOB), 0, 0));
             }
         };
         const float slope = p.slope;
@@ -178,11 +141,11 @@ convbf1_kernel(const Cb1Params p) {
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const float va = xr[i][2 * e2], vb = xr[i][2 * e2 + 1];
-                    cb_split3_np(__builtin_fmaxf(va, cb_mul_np(va, slope)), __builtin_fmaxf(vb, cb_mul_np(vb, slope)), w[e2]);
+                    split3_np(__builtin_fmaxf(va, mul_np(va, slope)), __builtin_fmaxf(vb, mul_np(vb, slope)), w[e2]);
                 }
                 unsigned char *o = xb + (r < XR ? r : GM::XROWS) * ROWB + qd * 8;
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<cb_u32x2 *>(o + s * 2 * CK) = cb_u32x2{w[0][s], w[1][s]};
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<u32x2 *>(o + s * 2 * CK) = u32x2{w[0][s], w[1][s]};
                 if (i & 1) __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -197,16 +160,16 @@ convbf1_kernel(const Cb1Params p) {
             const int bb = tl / p.tiles_per_row;
             const int64_t t0 = (int64_t)(tl - bb * p.tiles_per_row) * N1;
             const bool ok = t0 + 4 * chunk < L;
-            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * C * L), 0, num_bytes, CB1_RSRC_FLAGS);
-            const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)((has_res ? p.res : p.y) + (int64_t)bb * C * L), 0, num_bytes, CB1_RSRC_FLAGS);
-            const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)((has_acc ? p.accin : p.y) + (int64_t)bb * C * L), 0, num_bytes, CB1_RSRC_FLAGS);
-            const unsigned o0 = ok ? (unsigned)(sw * RPW + rsub) * L4 + (unsigned)(t0 + 4 * chunk) * 4u : CB1_OOB;
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
+            const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void *)((has_res ? p.res : p.y) + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
+            const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)((has_acc ? p.accin : p.y) + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
+            const unsigned o0 = ok ? (unsigned)(sw * RPW + rsub) * L4 + (unsigned)(t0 + 4 * chunk) * 4u : BUF_OOB;
             auto load4 = [&](const __amdgpu_buffer_rsrc_t &rsrc, unsigned o) __attribute__((always_inline)) -> f32x4 {
                 if (l4) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0));
                 float ae[4];                                  // rows not 16-byte aligned: element by element (past the row's end: zero)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : CB1_OOB;
+                    const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : BUF_OOB;
                     ae[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)oe, 0, 0));
                 }
                 return f32x4{ae[0], ae[1], ae[2], ae[3]};
@@ -231,16 +194,16 @@ convbf1_kernel(const Cb1Params p) {
                     const float r4[4] = {rv[k].x, rv[k].y, rv[k].z, rv[k].w}, a4[4] = {av[k].x, av[k].y, av[k].z, av[k].w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        if (has_res) re[e] = cb_add_np(re[e], r4[e]);
-                        if (has_acc) re[e] = cb_add_np(re[e], a4[e]);
-                        re[e] = cb_mul_np(re[e], out_scale);
+                        if (has_res) re[e] = add_np(re[e], r4[e]);
+                        if (has_acc) re[e] = add_np(re[e], a4[e]);
+                        re[e] = mul_np(re[e], out_scale);
                     }
                     if (l4) {
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(cb_u32x4, f32x4{re[0], re[1], re[2], re[3]}), yrs, (int)o, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{re[0], re[1], re[2], re[3]}), yrs, (int)o, 0, 0);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : CB1_OOB;
+                            const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : BUF_OOB;
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, re[e]), yrs, (int)oe, 0, 0);
                         }
                     }
@@ -280,25 +243,25 @@ convbf1_kernel(const Cb1Params p) {
             const int ch = 32 * (RBW * wave + rb) + (r & 3) + 8 * (r >> 2) + 4 * half;
             bias[rb][r] = p.bias ? p.bias[ch] : 0.f;
         }
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, GM::CONV_BYTES, CB1_RSRC_FLAGS);
-    cb_bf16x8 fa[PA][RBW];
-    cb_bf16x8 fb[2][2][3];
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, GM::CONV_BYTES, RSRC_RAW32);
+    bf16x8 fa[PA][RBW];
+    bf16x8 fb[2][2][3];
     f32x16 acc[RBW][2];
     // group g (of the tile, 0 .. NGT - 1; the stream wraps: every tile uses the same taps): this wave's RBW row blocks
     auto load_a = [&](int slot_a, int g) __attribute__((always_inline)) {
         const int soff = (g * GM::ROWBLOCKS + RBW * wave) * 1024;
 #pragma unroll
         for (int rb = 0; rb < RBW; ++rb)
-            fa[slot_a][rb] = __builtin_bit_cast(cb_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + rb * 1024, soff, 0));
+            fa[slot_a][rb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + rb * 1024, soff, 0));
     };
     auto load_a1 = [&](int slot_a, int g, int rb) __attribute__((always_inline)) {
         const int soff = (g * GM::ROWBLOCKS + RBW * wave) * 1024;
-        fa[slot_a][rb] = __builtin_bit_cast(cb_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + rb * 1024, soff, 0));
+        fa[slot_a][rb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + rb * 1024, soff, 0));
     };
     // one window fragment of group gc (of the chunk): (column tile cb, split s)
     auto load_b1 = [&](int buf, const unsigned char *src, int gc, int cb, int s) __attribute__((always_inline)) {
         const int tap = gc / KS, ks = gc - tap * KS;
-        fb[buf][cb][s] = __builtin_bit_cast(cb_bf16x8, *reinterpret_cast<const cb_u32x4 *>(src + tap * d * ROWB + ks * 32 + cb * 32 * ROWB + s * 2 * CK));
+        fb[buf][cb][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(src + tap * d * ROWB + ks * 32 + cb * 32 * ROWB + s * 2 * CK));
     };
 #pragma unroll
     for (int g = 0; g < PA - 1; ++g) load_a(g, g);
@@ -382,7 +345,7 @@ bool convbf1_preferred(int c, int k) {
     return (c == 128 && k == 11) || c == 256;
 }
 
-bool convbf1_fits(int c, int64_t L) { return (int64_t)c * L * 4 < ((int64_t)1 << 31); }
+bool convbf1_fits(int c, int64_t L) { return fits_2gib((int64_t)c * L, 4); }
 
 size_t convbf1_weight_bytes(int c, int k) { return (size_t)(c / 16) * k * (c / 32) * 1024; }
 
@@ -404,24 +367,14 @@ void convbf1_pack_host(const float *w, int c, int k, std::vector<uint16_t> *out)
                         }
 }
 
-static int cb1_cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
-}
-
 template <int KW, int C>
 static int cb1_launch(Cb1Params p, int batch, hipStream_t stream) {
     if (reserve_whole_cu((const void *)convbf1_kernel<KW, C>, "convbf1")) return 1;
     p.tiles_per_row = (int)ceil_div(p.L, CB1_N1);
     p.n_tiles = p.tiles_per_row * batch;
-    p.per_xcd = (int)ceil_div(p.n_tiles, 8);
-    const int cus = cb1_cu_count() / 8 * 8;
-    const int slots = (int)std::min<int64_t>(cus / 8, p.per_xcd);           // blocks per XCD
-    hipLaunchKernelGGL((convbf1_kernel<KW, C>), dim3((unsigned)(slots * 8)), dim3(CB1_NTH), LDS_WHOLE_CU, stream, p);   // owns its CU (common.h)
+    const PersistentGrid g = persistent_grid(p.n_tiles);
+    p.per_xcd = g.per_xcd;
+    hipLaunchKernelGGL((convbf1_kernel<KW, C>), dim3(g.blocks), dim3(CB1_NTH), LDS_WHOLE_CU, stream, p);   // owns its CU (common.h)
     RVC_LAUNCH_CHECK();
     return 0;
 }
@@ -461,10 +414,7 @@ extern "C" int rvc_conv1d_bf16w_pack_weight(const float *w_host, int c, int k, v
     if (rvc_conv1d_bf16w_weight_bytes(c, k, &bytes)) return 1;
     std::vector<uint16_t> u;
     convbf1_pack_host(w_host, c, k, &u);
-    hipError_t e = hipMemcpyAsync(u_dev, u.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_conv1d_bf16w_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_conv1d_bf16w_pack_weight", u.data(), bytes, u_dev, stream);
 }
 
 extern "C" int rvc_conv1d_bf16w_forward(const float *x_dev, const void *u_dev, const float *bias_dev, const float *res_dev,

@@ -879,7 +879,7 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
         const int64_t nq = len + 1;
         const int64_t len_out = (len - 1) * s.rate - 2 * s.pad + s.ksize + s.opad;
         float *X = buf[1];
-        if (s.wub.p && (int64_t)s.c_in * len * 4 < ((int64_t)1 << 31) && (int64_t)s.c_out * len_out * 4 < ((int64_t)1 << 31) && L * 4 < ((int64_t)1 << 31)) {
+        if (s.wub.p && fits_2gib((int64_t)s.c_in * len, 4) && fits_2gib((int64_t)s.c_out * len_out, 4) && fits_2gib(L, 4)) {
             if (launch_upsbf(cur, har, L, s.wub.p, s.b.p, X, batch, s.c_in, s.c_out, len, len_out, s.rate, s.ksize, s.pad, s.ub_vk, s.S, s.P, 0.1f, stream))
                 return 1;
         } else {

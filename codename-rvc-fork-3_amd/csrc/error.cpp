@@ -1,4 +1,4 @@
-// Thread-local last-error string behind the C ABI (include/rvc_amd.h: rvc_last_error).
+// Thread-local last-error string behind the C ABI (include/rvc_amd.h: rvc_last_error), and the host helpers common.h declares.
 #include <stdarg.h>
 
 #include <mutex>
@@ -37,6 +37,22 @@ int reserve_whole_cu(const void *kernel, const char *what) {
     const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
     if (e != hipSuccess) return fail("%s: cannot reserve %d bytes of LDS on device %d: %s", what, LDS_WHOLE_CU, dev, hipGetErrorString(e));
     if (dev < 64) done[dev].insert(kernel);   // (beyond 64 devices: set it every time -- it is cheap)
+    return 0;
+}
+
+int cu_count() {
+    static const int n = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+        return cus > 0 ? cus : 256;
+    }();
+    return n;
+}
+
+int upload_packed(const char *fn, const void *host, size_t bytes, void *dev, void *stream) {
+    hipError_t e = hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return fail("%s: %s", fn, hipGetErrorString(e));
     return 0;
 }
 

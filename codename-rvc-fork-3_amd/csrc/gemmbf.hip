@@ -59,10 +59,6 @@ constexpr int GBF_LDS_USED = 3 * GBF_A_SLOT + 2 * GBF_B_SLOT;
 constexpr int GBF_LDS = LDS_WHOLE_CU;               // requested: the whole CU (common.h)
 static_assert(GBF_LDS_USED <= GBF_LDS, "");
 
-typedef float gbf_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 gbf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 gbf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned gbf_u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3))) *gbf_lptr_t;
 
 // DBG (ablations, wrong results): 1 no activation staging after the prologue, 2 no matrix instructions, 4 no tap DMA, 8 no barrier
@@ -89,7 +85,7 @@ gemmbf_kernel(const GemmBfParams p) {
     const int n_steps = p.K / 16;
     const float *const x = p.x + (int64_t)bz * p.x_bstride;
 
-    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.M * p.K * 6), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.M * p.K * 6), RSRC_RAW32);
     const int blk_base = mblk * n_steps * GBF_A_SLOT;
     auto dma_a = [&](int s) __attribute__((always_inline)) {
         unsigned char *dst = as + (s % 3) * GBF_A_SLOT;
@@ -142,21 +138,18 @@ gemmbf_kernel(const GemmBfParams p) {
         for (int e = 0; e < LX_PIECES; ++e) load_x_piece(e);
     };
     // exact three-way split of the 8 values -> three 16-byte B-fragment pieces
-    gbf_u32x4 sw[3];
+    u32x4 sw[3];
     auto split_pair = [&](int e2) __attribute__((always_inline)) {
-        gbf_f32x2 v = {xv[2 * e2], xv[2 * e2 + 1]};
-        if (XMODE == 0 ? !col_ok : !lx_ok_prev) v = gbf_f32x2{0.f, 0.f};
-        const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, gbf_bf16x2));
-        const gbf_f32x2 r1 = v - gbf_f32x2{__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u)};
-        const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, gbf_bf16x2));
-        const gbf_f32x2 r2 = r1 - gbf_f32x2{__uint_as_float(w1 << 16), __uint_as_float(w1 & 0xffff0000u)};
-        const unsigned w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, gbf_bf16x2));
-        sw[0][e2] = w0; sw[1][e2] = w1; sw[2][e2] = w2;
+        f32x2 v = {xv[2 * e2], xv[2 * e2 + 1]};
+        if (XMODE == 0 ? !col_ok : !lx_ok_prev) v = f32x2{0.f, 0.f};
+        unsigned w[3];
+        split3(v, w);
+        sw[0][e2] = w[0]; sw[1][e2] = w[1]; sw[2][e2] = w[2];
     };
     auto store_split = [&](int s) __attribute__((always_inline)) {
         unsigned char *dst = bs + (s & 1) * GBF_B_SLOT + kh * GBF_B_PLANE + t_l * 16;
 #pragma unroll
-        for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<gbf_u32x4 *>(dst + sp * 2 * GBF_B_PLANE) = sw[sp];
+        for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<u32x4 *>(dst + sp * 2 * GBF_B_PLANE) = sw[sp];
     };
     auto store_x = [&](int s) __attribute__((always_inline)) {
 #pragma unroll
@@ -171,7 +164,7 @@ gemmbf_kernel(const GemmBfParams p) {
         for (int r = 0; r < 16; ++r) acc[i >> 1][i & 1][r] = 0.f;
 
     auto rd = [&](const unsigned char *ptr) __attribute__((always_inline)) {
-        return __builtin_bit_cast(gbf_bf16x8, *reinterpret_cast<const gbf_u32x4 *>(ptr));
+        return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(ptr));
     };
 
     // ---- prologue: steps 0 and 1 of the tap stream, step 0 of the activations in LDS, step 1 in registers -----------------
@@ -210,12 +203,12 @@ gemmbf_kernel(const GemmBfParams p) {
                 if (more2 && !(DBG & 1)) load_x_piece(k - 9);
             }
         };
-        gbf_bf16x8 fb[2][3];
+        bf16x8 fb[2][3];
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) fb[ni][sp] = rd(bb + sp * 2 * GBF_B_PLANE + ni * 32 * 16);
-        gbf_bf16x8 fa[2][3];
+        bf16x8 fa[2][3];
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) fa[0][sp] = rd(ab + sp * 1024);
         __builtin_amdgcn_sched_barrier(0);
@@ -326,16 +319,10 @@ static void gemmbf_pack_rows(const float *w, int M, int K, std::vector<uint16_t>
                 for (int lane = 0; lane < 64; ++lane)
                     for (int e = 0; e < 8; ++e) {
                         const int m = mb * GBF_BM + mi * 32 + (lane & 31), k = 16 * s + 8 * (lane >> 5) + e;
-                        float r = w[(size_t)m * K + k];
-                        for (int sp = 0; sp < 3; ++sp) {
-                            const uint16_t h = bf16_rne(r);
-                            uint32_t bits = (uint32_t)h << 16;
-                            float f;
-                            memcpy(&f, &bits, 4);
-                            r -= f;   // exact in fp32
-                            const size_t piece = (((size_t)mb * n_steps + s) * 4 + mi) * 3 + sp;
-                            (*out)[piece * 512 + lane * 8 + e] = h;
-                        }
+                        uint16_t h[3];
+                        bf16_split_host(w[(size_t)m * K + k], 3, h);
+                        const size_t piece = (((size_t)mb * n_steps + s) * 4 + mi) * 3;
+                        for (int sp = 0; sp < 3; ++sp) (*out)[(piece + sp) * 512 + lane * 8 + e] = h[sp];
                     }
 }
 
@@ -365,10 +352,7 @@ extern "C" int rvc_gemm_bf16x3_pack_weight(const float *w_host, int m, int k_tot
         std::vector<uint16_t> packed1;
         gemmbf_pack_rows(rows.data(), m, 16, &packed1);
         if (packed1.size() * sizeof(uint16_t) != bytes) return fail("rvc_gemm_bf16x3_pack_weight: internal size mismatch");
-        hipError_t e1 = hipMemcpyAsync(a_dev, packed1.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-        if (e1 == hipSuccess) e1 = hipStreamSynchronize((hipStream_t)stream);
-        if (e1 != hipSuccess) return fail("rvc_gemm_bf16x3_pack_weight: %s", hipGetErrorString(e1));
-        return 0;
+        return upload_packed("rvc_gemm_bf16x3_pack_weight", packed1.data(), bytes, a_dev, stream);
     }
     if (conv_taps > 1) {   // conv weight [m][c_in][taps] -> [m][tap * c_in + ci]
         if (k_total % conv_taps || (k_total / conv_taps) % 16) return fail("rvc_gemm_bf16x3_pack_weight: c_in must be a multiple of 16");
@@ -383,17 +367,14 @@ extern "C" int rvc_gemm_bf16x3_pack_weight(const float *w_host, int m, int k_tot
     std::vector<uint16_t> packed;
     gemmbf_pack_rows(w, m, k_total, &packed);
     if (packed.size() * sizeof(uint16_t) != bytes) return fail("rvc_gemm_bf16x3_pack_weight: internal size mismatch");
-    hipError_t e = hipMemcpyAsync(a_dev, packed.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_gemm_bf16x3_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_gemm_bf16x3_pack_weight", packed.data(), bytes, a_dev, stream);
 }
 
 extern "C" int rvc_linear_bf16x3(const float *x_dev, const void *a_dev, const float *bias_dev, const float *res_dev, float *y_dev,
                                  int64_t n_rows, int in_features, int out_features, int act, void *stream) {
     if (!x_dev || !a_dev || !y_dev) return fail("rvc_linear_bf16x3: null pointer");
     if (out_features % GBF_BM || in_features % 16) return fail("rvc_linear_bf16x3: out_features must be a multiple of 128, in_features of 16");
-    if ((int64_t)out_features * in_features * 6 >= ((int64_t)1 << 31)) return fail("rvc_linear_bf16x3: weight slab exceeds 2 GiB");
+    if (!fits_2gib((int64_t)out_features * in_features, 6)) return fail("rvc_linear_bf16x3: weight slab exceeds 2 GiB");
     if (act < 0 || act > 1) return fail("rvc_linear_bf16x3: act must be 0 (none) or 1 (gelu)");
     if (n_rows <= 0) return 0;
     GemmBfParams p;
@@ -410,7 +391,7 @@ extern "C" int rvc_conv1d_bf16x3(const float *x_dev, const void *a_dev, const fl
     if (one_channel && (k > 16 || padding != 0 || batch != 1))
         return fail("rvc_conv1d_bf16x3: a single input channel takes <= 16 taps, no padding, batch 1");
     if (c_out % GBF_BM || (!one_channel && c_in % 16) || k < 1 || stride < 1 || padding < 0) return fail("rvc_conv1d_bf16x3: c_out must be a multiple of 128, c_in of 16");
-    if ((int64_t)c_out * c_in * k * 6 >= ((int64_t)1 << 31)) return fail("rvc_conv1d_bf16x3: weight slab exceeds 2 GiB");
+    if (!fits_2gib((int64_t)c_out * c_in * k, 6)) return fail("rvc_conv1d_bf16x3: weight slab exceeds 2 GiB");
     if (act < 0 || act > 1) return fail("rvc_conv1d_bf16x3: act must be 0 (none) or 1 (gelu)");
     // an input shorter than one window has NO output: C division truncates toward zero, so (l_in + 2 padding - k) / stride + 1 is 1
     // for a deficit below `stride` (l_in 2, k 3, stride 2), and the kernel would store one column the caller never allocated

@@ -129,7 +129,6 @@ template <int CTRL>
 __device__ __forceinline__ float gru_dpp(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
-typedef float gru_f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float gru_rcp(float d) {   // d in [1, 2^120]: v_rcp_f32 (1 ulp) + one Newton step
     const float r = __builtin_amdgcn_rcpf(d);
@@ -169,12 +168,12 @@ bigru_x_kernel(const float *__restrict__ gi, const float *__restrict__ whhT, con
     const int ks = tid % KSL, ul = tid / KSL;
     const int u = c * UNITS + ul;
     const float *W = whhT + (size_t)dir * GRU_H * GRU_G + (size_t)(ks * KPT) * GRU_G + u;
-    gru_f32x2 wr[KPT / 2], wz[KPT / 2], wn[KPT / 2];
+    f32x2 wr[KPT / 2], wz[KPT / 2], wn[KPT / 2];
 #pragma unroll
     for (int i = 0; i < KPT / 2; ++i) {
-        wr[i] = gru_f32x2{W[(size_t)(2 * i) * GRU_G], W[(size_t)(2 * i + 1) * GRU_G]};
-        wz[i] = gru_f32x2{W[(size_t)(2 * i) * GRU_G + GRU_H], W[(size_t)(2 * i + 1) * GRU_G + GRU_H]};
-        wn[i] = gru_f32x2{W[(size_t)(2 * i) * GRU_G + 2 * GRU_H], W[(size_t)(2 * i + 1) * GRU_G + 2 * GRU_H]};
+        wr[i] = f32x2{W[(size_t)(2 * i) * GRU_G], W[(size_t)(2 * i + 1) * GRU_G]};
+        wz[i] = f32x2{W[(size_t)(2 * i) * GRU_G + GRU_H], W[(size_t)(2 * i + 1) * GRU_G + GRU_H]};
+        wn[i] = f32x2{W[(size_t)(2 * i) * GRU_G + 2 * GRU_H], W[(size_t)(2 * i + 1) * GRU_G + 2 * GRU_H]};
     }
     float *outb = out + (size_t)b * T * 2 * GRU_H + dir * GRU_H + u;
     const float b_r = bhh[dir * GRU_G + u], b_z = bhh[dir * GRU_G + GRU_H + u], b_n = bhh[dir * GRU_G + 2 * GRU_H + u];
@@ -215,11 +214,11 @@ bigru_x_kernel(const float *__restrict__ gi, const float *__restrict__ whhT, con
         const float *gs = &g_s[(s / GCH) & 1][(s % GCH) * 3 * UNITS + ul];
         const float gr = gs[0], gz = gs[UNITS], gn = gs[2 * UNITS];
         const float4 *hq = reinterpret_cast<const float4 *>(&h_s[par][ks * HST]);
-        gru_f32x2 ar = {0.f, 0.f}, az = {0.f, 0.f}, an = {0.f, 0.f};
+        f32x2 ar = {0.f, 0.f}, az = {0.f, 0.f}, an = {0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < KPT / 4; ++i) {
             const float4 hv = hq[i];
-            const gru_f32x2 h01 = {hv.x, hv.y}, h23 = {hv.z, hv.w};
+            const f32x2 h01 = {hv.x, hv.y}, h23 = {hv.z, hv.w};
             ar = __builtin_elementwise_fma(wr[2 * i], h01, ar); az = __builtin_elementwise_fma(wz[2 * i], h01, az); an = __builtin_elementwise_fma(wn[2 * i], h01, an);
             ar = __builtin_elementwise_fma(wr[2 * i + 1], h23, ar); az = __builtin_elementwise_fma(wz[2 * i + 1], h23, az); an = __builtin_elementwise_fma(wn[2 * i + 1], h23, an);
         }

@@ -15,10 +15,6 @@
 
 namespace rvc {
 
-typedef float hf_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 hf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned hf_u32x4 __attribute__((ext_vector_type(4)));
-
 // conv output of one (frame, channel): the SAME chain in both passes
 template <int TAPS>
 __device__ __forceinline__ float hf_conv(const float (&x)[TAPS], const float *w) {
@@ -135,17 +131,16 @@ hubert_conv0_apply_kernel(const float *__restrict__ wav, int64_t n_frames, int s
             const float n = ((o[e] - tab[c]) - tab[4 * C + c]) * tab[C + c] * tab[2 * C + c] + tab[3 * C + c];
             o[e] = 0.5f * n * (1.f + erff(n * 0.70710678118654752f));
         }
-        hf_f32x2 v[4] = {{o[0], o[1]}, {o[2], o[3]}, {o[4], o[5]}, {o[6], o[7]}};
+        f32x2 v[4] = {{o[0], o[1]}, {o[2], o[3]}, {o[4], o[5]}, {o[6], o[7]}};
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) {
-            hf_u32x4 pk;
+            u32x4 pk;
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                const unsigned wd = __builtin_bit_cast(unsigned, __builtin_convertvector(v[h], hf_bf16x2));
-                pk[h] = wd;
-                v[h] = v[h] - hf_f32x2{__uint_as_float(wd << 16), __uint_as_float(wd & 0xffff0000u)};
+                pk[h] = split_word(v[h]);
+                v[h] = split_rest(v[h], pk[h]);
             }
-            *reinterpret_cast<hf_u32x4 *>(ys + (((int64_t)sp * n_pad + t) * C + c0) * 2) = pk;
+            *reinterpret_cast<u32x4 *>(ys + (((int64_t)sp * n_pad + t) * C + c0) * 2) = pk;
         }
     }
 }

@@ -50,11 +50,6 @@ struct LinBfParams {
 constexpr int LBF_BN = 128, LBF_NTH = 512;
 constexpr int LBF_SLAB_STEP = 12 * 1024;                 // one 16-deep step of a 128-row block of the weight slab: [32-row block 4][split 3][1 KiB]
 constexpr int LBF_B_CHUNK = 3 * LBF_BN * 64;             // TWO steps of the activations: [split 3][row 128][32 features = 64 bytes]
-typedef float lbf_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 lbf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 lbf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned lbf_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned lbf_u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3))) *lbf_lptr_t;
 
 // MI = 32-row blocks per wave: 2 -> 128 output features per block, chunks requested two ahead; 3 -> 192 per block (16 x 13 = 208
@@ -106,8 +101,8 @@ linbf_kernel(const LinBfParams p) {
     const int n_chunks = p.steps_per_part / 2, s_first = part * p.steps_per_part;
     const int K = p.K;
 
-    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.M * K * 6), 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.xs, 0, (int)(3 * p.x_plane * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.M * K * 6), RSRC_RAW32);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)p.xs, 0, (int)(3 * p.x_plane * 2), RSRC_RAW32);
     const int slab_row = (K / 16) * LBF_SLAB_STEP;           // bytes of one 128-row block of the slab
     const int plane = (int)(p.x_plane * 2);
     const int row_bytes = (int)(p.x_row_stride * 2);
@@ -143,7 +138,7 @@ linbf_kernel(const LinBfParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][r] = 0.f;
     auto rd = [&](const unsigned char *ptr) __attribute__((always_inline)) {
-        return __builtin_bit_cast(lbf_bf16x8, *reinterpret_cast<const lbf_u32x4 *>(ptr));
+        return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(ptr));
     };
     const int nrow = wn * 32 + l31;                           // this lane's frame inside the tile
     const int b_lane = nrow * 64, b_sw = (nrow >> 2) & 3;
@@ -165,7 +160,7 @@ linbf_kernel(const LinBfParams p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const unsigned char *ab = a_ring + ((2 * c + t) % A_RING) * A_STEP + wm * MI * 3 * 1024 + lane * 16;
-            lbf_bf16x8 fa[MI][3], fb[3];
+            bf16x8 fa[MI][3], fb[3];
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) fb[sp] = rd(bslot + sp * (LBF_BN * 64) + (((2 * t + half) ^ b_sw) * 16));
 #pragma unroll
@@ -199,7 +194,7 @@ linbf_kernel(const LinBfParams p) {
             const int mb = m0 + wm * 32 * MI + mi * 32;
 #pragma unroll
             for (int rp = 0; rp < 2; ++rp) {                // register groups 2 rp (features 16 rp + 0..7), 2 rp + 1 (16 rp + 8..15)
-                lbf_f32x2 v[2][2];
+                f32x2 v[2][2];
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
                     f32x4 o;
@@ -208,8 +203,8 @@ linbf_kernel(const LinBfParams p) {
                     if (p.bias) o += *reinterpret_cast<const f32x4 *>(p.bias + mb + 4 * half + 8 * (2 * rp + g));
 #pragma unroll
                     for (int r = 0; r < 4; ++r) o[r] = 0.5f * o[r] * (1.f + erff(o[r] * 0.70710678118654752f));
-                    v[g][0] = lbf_f32x2{o[0], o[1]};
-                    v[g][1] = lbf_f32x2{o[2], o[3]};
+                    v[g][0] = f32x2{o[0], o[1]};
+                    v[g][1] = f32x2{o[2], o[3]};
                 }
 #pragma unroll
                 for (int sp = 0; sp < 3; ++sp) {
@@ -218,15 +213,15 @@ linbf_kernel(const LinBfParams p) {
                     for (int g = 0; g < 2; ++g)
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
-                            w[g][h] = __builtin_bit_cast(unsigned, __builtin_convertvector(v[g][h], lbf_bf16x2));
-                            v[g][h] = v[g][h] - lbf_f32x2{__uint_as_float(w[g][h] << 16), __uint_as_float(w[g][h] & 0xffff0000u)};
+                            w[g][h] = split_word(v[g][h]);
+                            v[g][h] = split_rest(v[g][h], w[g][h]);
                         }
                     // half 0 keeps group 2 rp and receives the partner's quad of it; half 1 keeps group 2 rp + 1
                     const unsigned s0 = half ? w[0][0] : w[1][0], s1 = half ? w[0][1] : w[1][1];
                     const unsigned r0 = (unsigned)__shfl_xor((int)s0, 32, 64), r1 = (unsigned)__shfl_xor((int)s1, 32, 64);
-                    const lbf_u32x4 out = half ? lbf_u32x4{r0, r1, w[1][0], w[1][1]} : lbf_u32x4{w[0][0], w[0][1], r0, r1};
+                    const u32x4 out = half ? u32x4{r0, r1, w[1][0], w[1][1]} : u32x4{w[0][0], w[0][1], r0, r1};
                     const int m = mb + 16 * rp + 8 * half;
-                    if (live) *reinterpret_cast<lbf_u32x4 *>(reinterpret_cast<unsigned char *>(p.ys) + (((int64_t)sp * p.n_pad + n) * p.M + m) * 2) = out;
+                    if (live) *reinterpret_cast<u32x4 *>(reinterpret_cast<unsigned char *>(p.ys) + (((int64_t)sp * p.n_pad + n) * p.M + m) * 2) = out;
                 }
             }
         }
@@ -267,14 +262,13 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float *__restrict
     const int64_t total4 = n_rows * k / 4;
     if (i4 >= total4) return;
     const f32x4 v = *reinterpret_cast<const f32x4 *>(x + i4 * 4);
-    lbf_f32x2 v0 = {v.x, v.y}, v1 = {v.z, v.w};
+    f32x2 v0 = {v.x, v.y}, v1 = {v.z, v.w};
 #pragma unroll
     for (int sp = 0; sp < 3; ++sp) {
-        const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, lbf_bf16x2));
-        const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, lbf_bf16x2));
-        *reinterpret_cast<lbf_u32x2 *>(xs + ((int64_t)sp * n_pad * k + i4 * 4) * 2) = lbf_u32x2{w0, w1};
-        v0 = v0 - lbf_f32x2{__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u)};
-        v1 = v1 - lbf_f32x2{__uint_as_float(w1 << 16), __uint_as_float(w1 & 0xffff0000u)};
+        const unsigned w0 = split_word(v0), w1 = split_word(v1);
+        *reinterpret_cast<u32x2 *>(xs + ((int64_t)sp * n_pad * k + i4 * 4) * 2) = u32x2{w0, w1};
+        v0 = split_rest(v0, w0);
+        v1 = split_rest(v1, w1);
     }
 }
 
@@ -330,14 +324,13 @@ __global__ void __launch_bounds__(256) ln_reduce_kernel(const float *__restrict_
         if (beta) o += *reinterpret_cast<const f32x4 *>(beta + m);
         if (y) *reinterpret_cast<f32x4 *>(y + n * M + m) = o;
         if (ys) {
-            lbf_f32x2 v0 = {o.x, o.y}, v1 = {o.z, o.w};
+            f32x2 v0 = {o.x, o.y}, v1 = {o.z, o.w};
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
-                const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, lbf_bf16x2));
-                const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, lbf_bf16x2));
-                *reinterpret_cast<lbf_u32x2 *>(ys + (((int64_t)sp * n_pad + n) * M + m) * 2) = lbf_u32x2{w0, w1};
-                v0 = v0 - lbf_f32x2{__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u)};
-                v1 = v1 - lbf_f32x2{__uint_as_float(w1 << 16), __uint_as_float(w1 & 0xffff0000u)};
+                const unsigned w0 = split_word(v0), w1 = split_word(v1);
+                *reinterpret_cast<u32x2 *>(ys + (((int64_t)sp * n_pad + n) * M + m) * 2) = u32x2{w0, w1};
+                v0 = split_rest(v0, w0);
+                v1 = split_rest(v1, w1);
             }
         }
     }
@@ -380,8 +373,8 @@ int linbf_dispatch(const char *who, const void *xs_dev, int64_t x_row_stride, in
     if (k_parts < 1 || (in_features / 32) % k_parts || in_features % 32) return fail("%s: in_features must be a multiple of 32 and k_parts divide in_features / 32", who);
     if (k_parts > 1 && mode != 2) return fail("%s: several K parts only produce partial sums (mode 2)", who);
     if (n_rows_padded % LBF_BN || n_rows_padded < n_rows) return fail("%s: n_rows_padded must be a multiple of 128 and >= n_rows", who);
-    if ((int64_t)out_features * in_features * 6 >= ((int64_t)1 << 31) || 3 * x_plane * 2 >= ((int64_t)1 << 31) ||
-        (n_rows_padded + LBF_BN) * x_row_stride * 2 >= ((int64_t)1 << 31))
+    if (!fits_2gib((int64_t)out_features * in_features, 6) || !fits_2gib(3 * x_plane, 2) ||
+        !fits_2gib((n_rows_padded + LBF_BN) * x_row_stride, 2))
         return fail("%s: an operand exceeds 2 GiB", who);
     if (x_row_stride % 8) return fail("%s: rows must start on 16-byte boundaries", who);
     if (n_rows <= 0) return 0;

@@ -34,11 +34,6 @@ struct PosConvParams {
     int D = 0, groups = 0, taps = 0, pad = 0;
 };
 
-typedef float pc_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 pc_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 pc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned pc_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned pc_u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3))) *pc_lptr_t;
 
 constexpr int PC_BN = 128, PC_NTH = 512;
@@ -64,7 +59,7 @@ posconv_kernel(const PosConvParams p) {
     const int plane = R * WS;
 
     const __amdgpu_buffer_rsrc_t ars =
-        __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.groups * KT * CHUNK), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc((void *)p.a, 0, (int)((int64_t)p.groups * KT * CHUNK), RSRC_RAW32);
     const int a_group = g * KT * CHUNK;
     // piece q of a chunk = (step cc, row tile, split); the second row tile's lanes with rows >= CG read outside the buffer: zeros, no fetch
     auto dma = [&](int k) __attribute__((always_inline)) {
@@ -90,14 +85,13 @@ posconv_kernel(const PosConvParams p) {
             const int64_t t = t0 - p.pad + r;
             const bool in = t >= 0 && t < p.T;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(xg + (in ? t : 0) * p.D + 4 * c4);
-            pc_f32x2 v0 = {in ? v.x : 0.f, in ? v.y : 0.f}, v1 = {in ? v.z : 0.f, in ? v.w : 0.f};
+            f32x2 v0 = {in ? v.x : 0.f, in ? v.y : 0.f}, v1 = {in ? v.z : 0.f, in ? v.w : 0.f};
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
-                const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, pc_bf16x2));
-                const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, pc_bf16x2));
-                *reinterpret_cast<pc_u32x2 *>(win + sp * plane + r * WS + c4 * 8) = pc_u32x2{w0, w1};
-                v0 = v0 - pc_f32x2{__uint_as_float(w0 << 16), __uint_as_float(w0 & 0xffff0000u)};
-                v1 = v1 - pc_f32x2{__uint_as_float(w1 << 16), __uint_as_float(w1 & 0xffff0000u)};
+                const unsigned w0 = split_word(v0), w1 = split_word(v1);
+                *reinterpret_cast<u32x2 *>(win + sp * plane + r * WS + c4 * 8) = u32x2{w0, w1};
+                v0 = split_rest(v0, w0);
+                v1 = split_rest(v1, w1);
             }
         }
     }
@@ -110,14 +104,14 @@ posconv_kernel(const PosConvParams p) {
     const unsigned char *const a_lane = ring + rt * 3 * 1024 + lane * 16;
     const unsigned char *const b_lane = win + (ct * 32 + l31) * WS + half * 16;
     auto rd = [&](const unsigned char *ptr) __attribute__((always_inline)) {
-        return __builtin_bit_cast(pc_bf16x8, *reinterpret_cast<const pc_u32x4 *>(ptr));
+        return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(ptr));
     };
     for (int k = 0; k < KT; ++k) {
         if (k + 1 < KT) dma(k + 1);
         const unsigned char *ab = a_lane + (k & 1) * CHUNK, *bb = b_lane + k * WS;
 #pragma unroll
         for (int cc = 0; cc < NCC; ++cc) {
-            pc_bf16x8 fa[3], fb[3];
+            bf16x8 fa[3], fb[3];
 #pragma unroll
             for (int sp = 0; sp < 3; ++sp) {
                 fa[sp] = rd(ab + (cc * 6 + sp) * 1024);
@@ -163,16 +157,10 @@ static void posconv_pack_host(const float *w, int D, int groups, int taps, std::
                         if (o >= CG) continue;
                         for (int e = 0; e < 8; ++e) {
                             const int c = cc * 16 + 8 * (lane >> 5) + e;
-                            float r = w[((size_t)(g * CG + o) * CG + c) * taps + k];
-                            for (int sp = 0; sp < 3; ++sp) {
-                                const uint16_t h = bf16_rne(r);
-                                uint32_t bits = (uint32_t)h << 16;
-                                float f;
-                                memcpy(&f, &bits, 4);
-                                r -= f;   // exact in fp32
-                                const size_t piece = ((((size_t)g * taps + k) * NCC + cc) * 2 + rt) * 3 + sp;
-                                (*out)[piece * 512 + lane * 8 + e] = h;
-                            }
+                            uint16_t h[3];
+                            bf16_split_host(w[((size_t)(g * CG + o) * CG + c) * taps + k], 3, h);
+                            const size_t piece = ((((size_t)g * taps + k) * NCC + cc) * 2 + rt) * 3;
+                            for (int sp = 0; sp < 3; ++sp) (*out)[(piece + sp) * 512 + lane * 8 + e] = h[sp];
                         }
                     }
 }
@@ -201,10 +189,7 @@ extern "C" int rvc_posconv_bf16x3_pack_weight(const float *w_host, int d, int gr
     std::vector<uint16_t> packed;
     posconv_pack_host(w_host, d, groups, taps, &packed);
     if (packed.size() * sizeof(uint16_t) != bytes) return fail("rvc_posconv_bf16x3_pack_weight: internal size mismatch");
-    hipError_t e = hipMemcpyAsync(a_dev, packed.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);   // the staging vector dies with this call
-    if (e != hipSuccess) return fail("rvc_posconv_bf16x3_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_posconv_bf16x3_pack_weight", packed.data(), bytes, a_dev, stream);
 }
 
 template <int CG>

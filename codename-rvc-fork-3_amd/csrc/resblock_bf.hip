@@ -38,15 +38,7 @@
 
 namespace rvc {
 
-typedef __bf16 rb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float rb_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned rb_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned rb_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int RBF_NTH = 512;
-constexpr int RBF_RSRC_FLAGS = 0x00020000;
-constexpr unsigned RBF_OOB = 0x80000000u;   // a buffer offset beyond every tensor this kernel takes: loads return 0, stores are dropped
 
 struct RbfParams {
     const float *x = nullptr;        // [batch][C][L]
@@ -59,37 +51,6 @@ struct RbfParams {
     float slope = 1.f, out_scale = 1.f;
     int tiles_per_row = 0, n_tiles = 0, per_xcd = 0;
 };
-
-// Plain (unpacked) fp32 VALU for code that runs NEXT TO another wave's matrix instructions on the same SIMD: v_pk_add_f32 /
-// v_pk_mul_f32 there waited ~100 cycles each (the stagers' 60 packed operations per tile took 7 800 cycles of a 20 000-cycle tile:
-// profiles/r05_rbf_stamps.txt); inline asm, so that neither the vector types nor the SLP vectoriser can pack them again.
-__device__ __forceinline__ float rb_sub_np(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float rb_add_np(float a, float b) {
-    float r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float rb_mul_np(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// (a, b) -> three words of two bf16 each whose sums are a and b exactly
-__device__ __forceinline__ void rb_split3_np(float a, float b, unsigned w[3]) {
-#pragma unroll
-    for (int level = 0; level < 3; ++level) {
-        const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(rb_f32x2{a, b}, rb_bf16x2));
-        w[level] = ww;
-        if (level < 2) {
-            a = rb_sub_np(a, __uint_as_float(ww << 16));
-            b = rb_sub_np(b, __uint_as_float(ww & 0xffff0000u));
-        }
-    }
-}
 
 // NTS = terms of the TAP split: 3 for fp32 taps (six products per multiply-add), 1 for bf16-VALUED taps (BASELINE cfg 4's weight
 // storage: w = w_0 exactly, so the three products w_0 x_0 + w_0 x_1 + w_0 x_2 are the whole result -- half the matrix instructions
@@ -117,16 +78,6 @@ struct RbfGeom {
     static_assert(LDS_BYTES <= 163840, "LDS budget");
     static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd multiple of 16 bytes");
 };
-
-// v -> three bf16 whose sum is v exactly (round to nearest even each time; the remainders are exact in fp32)
-__device__ __forceinline__ void rb_split3(rb_f32x2 v, unsigned w[3]) {
-#pragma unroll
-    for (int level = 0; level < 3; ++level) {
-        const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(v, rb_bf16x2));
-        w[level] = ww;
-        if (level < 2) v = v - rb_f32x2{__uint_as_float(ww << 16), __uint_as_float(ww & 0xffff0000u)};
-    }
-}
 
 // DBG (ablation build only): 128 = wave 0 and stager wave 4 write s_memtime stamps to the buffer passed as `accin` (which is then NOT
 // added): [block][compute | stager][64], eight per tile -- tools/stamp_resblock_bf.py turns them into a per-phase breakdown
@@ -185,7 +136,7 @@ resblock_bf_kernel(const RbfParams p) {
             constexpr int st = decltype(SET)::value;
             const int bb = tl / p.tiles_per_row;
             const int xt0 = (tl - bb * p.tiles_per_row) * BN - H2 - h1;                     // time of row 0 (a row holds < 2^29 samples)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * C * L), 0, num_bytes, RBF_RSRC_FLAGS);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
             const unsigned Lu = (unsigned)L;
             int sw_o = sw;                                    // opaque: the per-item scalars are recomputed here (a dozen scalar operations
             asm volatile("" : "+s"(sw_o));                    // per item) instead of being hoisted out of the tile loop and spilled (333 of them)
@@ -198,7 +149,7 @@ resblock_bf_kernel(const RbfParams p) {
                 const unsigned base = (unsigned)(4 * q) * L4 + tg * 4u;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    xr[st][i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : RBF_OOB), 0, 0));
+                    xr[st][i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : BUF_OOB), 0, 0));
             }
         };
         const float slope = p.slope;
@@ -215,11 +166,11 @@ resblock_bf_kernel(const RbfParams p) {
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const float va = xr[st][i][2 * e2], vb = xr[st][i][2 * e2 + 1];
-                    rb_split3_np(__builtin_fmaxf(va, rb_mul_np(va, slope)), __builtin_fmaxf(vb, rb_mul_np(vb, slope)), w[e2]);
+                    split3_np(__builtin_fmaxf(va, mul_np(va, slope)), __builtin_fmaxf(vb, mul_np(vb, slope)), w[e2]);
                 }
                 unsigned char *o = xs + (r < XR ? r : GM::XROWS) * ROWB + q * 8;
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<rb_u32x2 *>(o + s * 2 * C) = rb_u32x2{w[0][s], w[1][s]};
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<u32x2 *>(o + s * 2 * C) = u32x2{w[0][s], w[1][s]};
                 // the raw values of the block's own columns: the residual the compute waves add (lanes = consecutive columns of one row)
                 const int j = r - h1 - H2;
                 const bool own = r < XR && j >= 0 && j < N1;
@@ -238,9 +189,9 @@ resblock_bf_kernel(const RbfParams p) {
             const int bb = tl / p.tiles_per_row;
             const int64_t t0 = (int64_t)(tl - bb * p.tiles_per_row) * BN;
             const bool ok = 4 * chunk < BN && t0 + 4 * chunk < L;
-            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * C * L), 0, num_bytes, RBF_RSRC_FLAGS);
-            const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)((with_acc ? p.accin : p.y) + (int64_t)bb * C * L), 0, num_bytes, RBF_RSRC_FLAGS);
-            const unsigned o0 = ok ? (unsigned)(sw * RPW + rsub) * L4 + (unsigned)(t0 + 4 * chunk) * 4u : RBF_OOB;
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
+            const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void *)((with_acc ? p.accin : p.y) + (int64_t)bb * C * L), 0, num_bytes, RSRC_RAW32);
+            const unsigned o0 = ok ? (unsigned)(sw * RPW + rsub) * L4 + (unsigned)(t0 + 4 * chunk) * 4u : BUF_OOB;
             constexpr int HP = PASSES / 2;                    // two halves: registers (the x sets stay live next to this)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
@@ -257,7 +208,7 @@ resblock_bf_kernel(const RbfParams p) {
                             float ae[4];
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : RBF_OOB;
+                                const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : BUF_OOB;
                                 ae[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ars, (int)oe, 0, 0));
                             }
                             av[k] = f32x4{ae[0], ae[1], ae[2], ae[3]};
@@ -273,15 +224,15 @@ resblock_bf_kernel(const RbfParams p) {
                     const float ae[4] = {av[k].x, av[k].y, av[k].z, av[k].w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        if (with_acc) re[e] = rb_add_np(re[e], ae[e]);
-                        re[e] = rb_mul_np(re[e], out_scale);
+                        if (with_acc) re[e] = add_np(re[e], ae[e]);
+                        re[e] = mul_np(re[e], out_scale);
                     }
                     if (l4) {
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(rb_u32x4, f32x4{re[0], re[1], re[2], re[3]}), yrs, (int)o, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{re[0], re[1], re[2], re[3]}), yrs, (int)o, 0, 0);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : RBF_OOB;
+                            const unsigned oe = (ok && t0 + 4 * chunk + e < L) ? o + 4u * (unsigned)e : BUF_OOB;
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, re[e]), yrs, (int)oe, 0, 0);
                         }
                     }
@@ -290,7 +241,7 @@ resblock_bf_kernel(const RbfParams p) {
         };
         const bool has_acc = p.accin != nullptr && !(DBG & 128);
         // rows N1 .. TROWS-1 of the t tile are read by masked output columns only and never written: give them a value once
-        for (int o = ht * 16; o < (KW - 1) * ROWB; o += 256 * 16) *reinterpret_cast<rb_u32x4 *>(ts + N1 * ROWB + o) = rb_u32x4{0u, 0u, 0u, 0u};
+        for (int o = ht * 16; o < (KW - 1) * ROWB; o += 256 * 16) *reinterpret_cast<u32x4 *>(ts + N1 * ROWB + o) = u32x4{0u, 0u, 0u, 0u};
         // Tile i + 2 is requested behind barrier D of tile i and written behind barrier B of tile i + 1: a whole tile between request
         // and use.  Never more than one set + 8 stores in flight per wave, and tile 0 is written before tile 1 is requested: with the
         // prologue order (request 0, request 1, write 0) -- 96 loads in flight at C = 64 -- the SECOND tile of 4-18 blocks per launch
@@ -345,27 +296,27 @@ resblock_bf_kernel(const RbfParams p) {
         bias1[r] = p.b1 ? p.b1[ch] : 0.f;
         bias2[r] = p.b2 ? p.b2[ch] : 0.f;
     }
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, 2 * GM::CONV_BYTES, RBF_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, 2 * GM::CONV_BYTES, RSRC_RAW32);
     const float slope = p.slope;
 
-    rb_bf16x8 fa[PA][NTS];
-    rb_bf16x8 fb[2][2][3];
+    bf16x8 fa[PA][NTS];
+    bf16x8 fb[2][2][3];
     f32x16 acc[2];
     // group g = tap * KS + ks of conv `cv`: the three splits of this wave's row block
     auto load_a = [&](int slot_a, int cv, int g) __attribute__((always_inline)) {
         const int soff = cv * GM::CONV_BYTES + (g * RB + rb) * GM::GROUP_BYTES;
 #pragma unroll
         for (int s = 0; s < NTS; ++s)
-            fa[slot_a][s] = __builtin_bit_cast(rb_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + s * 1024, soff, 0));
+            fa[slot_a][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + s * 1024, soff, 0));
     };
     // one window fragment of group g: (column tile cb, split s)
     auto load_b1 = [&](int buf, const unsigned char *src, int tapstep, int g, int cb, int s) __attribute__((always_inline)) {
         const int tap = g / KS, ks = g - tap * KS;
-        fb[buf][cb][s] = __builtin_bit_cast(rb_bf16x8, *reinterpret_cast<const rb_u32x4 *>(src + tap * tapstep + ks * 32 + cb * 32 * ROWB + s * 2 * C));
+        fb[buf][cb][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(src + tap * tapstep + ks * 32 + cb * 32 * ROWB + s * 2 * C));
     };
     auto load_a1 = [&](int slot_a, int cv, int g, int s) __attribute__((always_inline)) {
         const int soff = cv * GM::CONV_BYTES + (g * RB + rb) * GM::GROUP_BYTES;
-        fa[slot_a][s] = __builtin_bit_cast(rb_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + s * 1024, soff, 0));
+        fa[slot_a][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + s * 1024, soff, 0));
     };
     auto a_prologue = [&](int cv) __attribute__((always_inline)) {
 #pragma unroll
@@ -457,15 +408,15 @@ resblock_bf_kernel(const RbfParams p) {
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const int r = 4 * jq + 2 * e2;
-                    const rb_f32x2 v = rb_f32x2{acc[cb][r] + bias1[r], acc[cb][r + 1] + bias1[r + 1]};
-                    const rb_f32x2 sv = v * slope;
-                    const rb_f32x2 a = rb_f32x2{__uint_as_float(__float_as_uint(__builtin_fmaxf(v.x, sv.x)) & keep),
+                    const f32x2 v = f32x2{acc[cb][r] + bias1[r], acc[cb][r + 1] + bias1[r + 1]};
+                    const f32x2 sv = v * slope;
+                    const f32x2 a = f32x2{__uint_as_float(__float_as_uint(__builtin_fmaxf(v.x, sv.x)) & keep),
                                                 __uint_as_float(__float_as_uint(__builtin_fmaxf(v.y, sv.y)) & keep)};
-                    rb_split3(a, w[e2]);
+                    split3(a, w[e2]);
                 }
                 unsigned char *o = ts + j * ROWB + (32 * rb + 8 * jq + 4 * half) * 2;
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<rb_u32x2 *>(o + s * 2 * C) = rb_u32x2{w[0][s], w[1][s]};
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<u32x2 *>(o + s * 2 * C) = u32x2{w[0][s], w[1][s]};
             }
         }
         stamp();
@@ -514,14 +465,12 @@ bool resblock_bf_preferred(int c, int k, int tap_splits) {
 #ifdef RVC_ABLATE
     static const int all = knob("RVC_RBF_ALL", 0);
     if (all) return true;
-    static const int one = knob("RVC_RBF_ONE", 1);       // 0: bf16-valued taps as three-term fragments (round 5's cfg 4)
-    if (tap_splits == 1 && !one) tap_splits = 3;
 #endif
     if (tap_splits == 1) return true;
     return c == 32 || (c == 64 && k != 11) || (c == 128 && k == 3);
 }
 
-bool resblock_bf_fits(int c, int64_t L) { return (int64_t)c * L * 4 < ((int64_t)1 << 31); }
+bool resblock_bf_fits(int c, int64_t L) { return fits_2gib((int64_t)c * L, 4); }
 
 size_t resblock_bf_weight_bytes(int c, int k, int tap_splits) { return (size_t)2 * k * (c / 16) * (c / 32) * tap_splits * 1024; }
 
@@ -539,27 +488,12 @@ void resblock_bf_pack_host(const float *w1, const float *w2, int c, int k, std::
                     for (int lane = 0; lane < 64; ++lane)
                         for (int e = 0; e < 8; ++e) {
                             const int co = 32 * rb + (lane & 31), ci = 16 * ks + 8 * (lane >> 5) + e;
-                            float r = w[((size_t)co * c + ci) * k + tap];
                             const size_t group = (((size_t)cv * k + tap) * KS + ks) * RB + rb;
-                            for (int s = 0; s < tap_splits; ++s) {
-                                const uint16_t h = bf16_rne(r);
-                                const uint32_t bits = (uint32_t)h << 16;
-                                float f;
-                                memcpy(&f, &bits, 4);
-                                r -= f;                      // exact in fp32
-                                (*out)[(group * tap_splits + s) * 512 + lane * 8 + e] = h;
-                            }
+                            uint16_t h[3];
+                            bf16_split_host(w[((size_t)co * c + ci) * k + tap], tap_splits, h);
+                            for (int s = 0; s < tap_splits; ++s) (*out)[(group * tap_splits + s) * 512 + lane * 8 + e] = h[s];
                         }
     }
-}
-
-static int rbf_cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
 }
 
 template <int KW, int C, int DBG = 0, int NTS = 3>
@@ -568,10 +502,9 @@ static int rbf_launch(RbfParams p, int batch, hipStream_t stream) {
     if (reserve_whole_cu((const void *)resblock_bf_kernel<KW, C, DBG, NTS>, "resblock_bf")) return 1;
     p.tiles_per_row = (int)ceil_div(p.L, GM::BN);
     p.n_tiles = p.tiles_per_row * batch;
-    p.per_xcd = (int)ceil_div(p.n_tiles, 8);
-    const int cus = rbf_cu_count() / 8 * 8;
-    const int slots = (int)std::min<int64_t>(cus / 8, p.per_xcd);           // blocks per XCD
-    hipLaunchKernelGGL((resblock_bf_kernel<KW, C, DBG, NTS>), dim3((unsigned)(slots * 8)), dim3(RBF_NTH), LDS_WHOLE_CU, stream, p);   // owns its CU (common.h)
+    const PersistentGrid g = persistent_grid(p.n_tiles);
+    p.per_xcd = g.per_xcd;
+    hipLaunchKernelGGL((resblock_bf_kernel<KW, C, DBG, NTS>), dim3(g.blocks), dim3(RBF_NTH), LDS_WHOLE_CU, stream, p);   // owns its CU (common.h)
     RVC_LAUNCH_CHECK();
     return 0;
 }
@@ -623,10 +556,7 @@ static int rbf_pack_abi(const char *fn, const float *w1_host, const float *w2_ho
     if (rbf_weight_bytes_abi(fn, c, k, tap_splits, &bytes)) return 1;
     std::vector<uint16_t> u;
     resblock_bf_pack_host(w1_host, w2_host, c, k, &u, tap_splits);
-    hipError_t e = hipMemcpyAsync(u_dev, u.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("%s: %s", fn, hipGetErrorString(e));
-    return 0;
+    return upload_packed(fn, u.data(), bytes, u_dev, stream);
 }
 
 extern "C" int rvc_resblock_bf16x3_weight_bytes(int c, int k, size_t *bytes) { return rbf_weight_bytes_abi("rvc_resblock_bf16x3_weight_bytes", c, k, 3, bytes); }

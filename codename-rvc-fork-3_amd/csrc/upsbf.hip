@@ -30,15 +30,7 @@
 
 namespace rvc {
 
-typedef __bf16 ub_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ub_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ub_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ub_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ub_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int UB_NTH = 512;
-constexpr int UB_RSRC_FLAGS = 0x00020000;
-constexpr unsigned UB_OOB = 0x80000000u;
 constexpr int UB_CK = 64;                   // input channels per chunk
 
 struct UbParams {
@@ -56,28 +48,6 @@ struct UbParams {
     float slope = 0.1f;
     int n_mblk = 0, col_tiles = 0, n_tiles = 0, per_xcd = 0;
 };
-
-__device__ __forceinline__ float ub_sub_np(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float ub_mul_np(float a, float b) {
-    float r;
-    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void ub_split3_np(float a, float b, unsigned w[3]) {
-#pragma unroll
-    for (int level = 0; level < 3; ++level) {
-        const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(ub_f32x2{a, b}, ub_bf16x2));
-        w[level] = ww;
-        if (level < 2) {
-            a = ub_sub_np(a, __uint_as_float(ww << 16));
-            b = ub_sub_np(b, __uint_as_float(ww & 0xffff0000u));
-        }
-    }
-}
 
 template <int R, int MB>
 struct UbGeom {
@@ -142,7 +112,7 @@ upsbf_kernel(const UbParams p) {
 
     // Both x buffers start as zeros: the noise chunk stages only the channel quads that hold noise rows (and the ones row), the products of
     // its other k steps multiply zero taps with whatever the buffer holds -- which must then be a finite number, not a stale bit pattern.
-    for (int o = tid * 16; o < 2 * GM::X_BYTES; o += UB_NTH * 16) *reinterpret_cast<ub_u32x4 *>(xs + o) = ub_u32x4{0u, 0u, 0u, 0u};
+    for (int o = tid * 16; o < 2 * GM::X_BYTES; o += UB_NTH * 16) *reinterpret_cast<u32x4 *>(xs + o) = u32x4{0u, 0u, 0u, 0u};
     lds_barrier();
     const int nqp_noise = (p.vk + 1 + 7) / 8;                 // channel quad PAIRS of the noise chunk that carry data
 
@@ -163,7 +133,7 @@ upsbf_kernel(const UbParams p) {
             int sw_o = sw;
             asm volatile("" : "+s"(sw_o));
             if (ci < nxc) {
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * p.c_in * L_in), 0, x_bytes, UB_RSRC_FLAGS);
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.x + (int64_t)bb * p.c_in * L_in), 0, x_bytes, RSRC_RAW32);
                 const unsigned Lu = (unsigned)L_in;
                 const int ch0 = ci * CK;
 #pragma unroll
@@ -175,11 +145,11 @@ upsbf_kernel(const UbParams p) {
                     const unsigned base = (unsigned)(ch0 + 4 * qd) * L4 + tg * 4u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : UB_OOB), 0, 0));
+                        xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? base + (unsigned)e * L4 : BUF_OOB), 0, 0));
                 }
             } else {
                 const int h_bytes = (int)(p.Lh * 4);
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.har + (int64_t)bb * p.Lh), 0, h_bytes, UB_RSRC_FLAGS);
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.har + (int64_t)bb * p.Lh), 0, h_bytes, RSRC_RAW32);
                 const int vk = p.vk;
 #pragma unroll
                 for (int i = 0; i < NIT; ++i) {
@@ -193,7 +163,7 @@ upsbf_kernel(const UbParams p) {
                     for (int e = 0; e < 4; ++e) {
                         const int64_t idx = idx0 + e;
                         const bool ok = okq && 4 * qd + e < vk && idx >= 0 && idx < p.Lh;
-                        xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? (unsigned)idx * 4u : UB_OOB), 0, 0));
+                        xr[i][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(ok ? (unsigned)idx * 4u : BUF_OOB), 0, 0));
                         if (4 * qd + e == vk) xr[i][e] = 1.f;   // the ONES row: its taps are the bias (upsbf_pack_host)
                     }
                 }
@@ -213,11 +183,11 @@ upsbf_kernel(const UbParams p) {
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const float va = xr[i][2 * e2], vb = xr[i][2 * e2 + 1];
-                    ub_split3_np(__builtin_fmaxf(va, ub_mul_np(va, slope)), __builtin_fmaxf(vb, ub_mul_np(vb, slope)), w[e2]);
+                    split3_np(__builtin_fmaxf(va, mul_np(va, slope)), __builtin_fmaxf(vb, mul_np(vb, slope)), w[e2]);
                 }
                 unsigned char *o = xb + (r < GM::XROWS ? r : GM::XROWS) * ROWB + qd * 8;
 #pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<ub_u32x2 *>(o + s * 2 * CK) = ub_u32x2{w[0][s], w[1][s]};
+                for (int s = 0; s < 3; ++s) *reinterpret_cast<u32x2 *>(o + s * 2 * CK) = u32x2{w[0][s], w[1][s]};
                 if (i & 1) __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -227,7 +197,7 @@ upsbf_kernel(const UbParams p) {
         auto out_store = [&](int tl) __attribute__((always_inline)) {
             int mblk, ct, bb;
             tile_coords(tl, mblk, ct, bb);
-            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * p.c_out * L_out), 0, y_bytes, UB_RSRC_FLAGS);
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(p.y + (int64_t)bb * p.c_out * L_out), 0, y_bytes, RSRC_RAW32);
             const int64_t t_base = (int64_t)ct * N1 * R - p.pad;
             const int m0 = mblk * MB, co0 = m0 / R;                    // the tile's first GEMM row / the channel of slot 0
             constexpr int n_el = GM::CPB * W;
@@ -244,7 +214,7 @@ upsbf_kernel(const UbParams p) {
                     const bool ok = f < n_el && m >= m0 && m < m0 + MB && m < m_total && t >= 0 && t < L_out;   // channel may be shared with a neighbour)
                     v[k] = io_lds[f < n_el ? f : 0];
                     bv[k] = !fold && p.bias && ok ? p.bias[co0 + row] : 0.f;
-                    off[k] = ok ? (unsigned)(co0 + row) * Lo4 + (unsigned)t * 4u : UB_OOB;
+                    off[k] = ok ? (unsigned)(co0 + row) * Lo4 + (unsigned)t * 4u : BUF_OOB;
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[k] + bv[k]), yrs, (int)off[k], 0, 0);
@@ -281,16 +251,16 @@ upsbf_kernel(const UbParams p) {
     // RB_T >= 4: wave w owns row blocks RBW w .. of all 64 columns; RB_T == 2: wave w owns row block w & 1 of column group w >> 1
     const int rb0 = RB_T >= 4 ? RBW * wave : wave % RB_T;
     const int col0 = RB_T >= 4 ? 0 : 64 * (wave / RB_T);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, n_mblk * ngt * GM::GROUP_BYTES, UB_RSRC_FLAGS);
-    ub_bf16x8 fa[PA][RBW][3];
-    ub_bf16x8 fb[2][2][3];
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, n_mblk * ngt * GM::GROUP_BYTES, RSRC_RAW32);
+    bf16x8 fa[PA][RBW][3];
+    bf16x8 fb[2][2][3];
     f32x16 acc[RBW][2];
     auto load_a1 = [&](int slot_a, int byte_off, int rb, int s) __attribute__((always_inline)) {
-        fa[slot_a][rb][s] = __builtin_bit_cast(ub_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + ((rb0 + rb) * 3 + s) * 1024, byte_off, 0));
+        fa[slot_a][rb][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + ((rb0 + rb) * 3 + s) * 1024, byte_off, 0));
     };
     auto load_b1 = [&](int buf, const unsigned char *src, int gc, int cb, int s) __attribute__((always_inline)) {
         const int j = gc / KS, ks = gc - j * KS;             // tap j reads LDS row (column + 1 - j)
-        fb[buf][cb][s] = __builtin_bit_cast(ub_bf16x8, *reinterpret_cast<const ub_u32x4 *>(src + (1 - j) * ROWB + ks * 32 + cb * 32 * ROWB + s * 2 * CK));
+        fb[buf][cb][s] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(src + (1 - j) * ROWB + ks * 32 + cb * 32 * ROWB + s * 2 * CK));
     };
     const int x_lane = (col0 + l31) * ROWB + half * 16;
     constexpr int ia6[6] = {0, 1, 0, 2, 1, 0}, ib6[6] = {2, 1, 1, 0, 0, 0};   // (tap split, window split): smallest products first
@@ -415,15 +385,9 @@ void upsbf_pack_host(const float *uw, const float *nw, const float *bias, int c_
     const int RB_T = mb / 32, nxc = c_in / UB_CK;
     out->assign(upsbf_weight_bytes(c_in, c_out, rate, vk) / 2, 0);
     auto put = [&](size_t group, int rb, int lane, int e, float v) {
-        float r = v;
-        for (int s = 0; s < 3; ++s) {
-            const uint16_t h = bf16_rne(r);
-            const uint32_t bits = (uint32_t)h << 16;
-            float f;
-            memcpy(&f, &bits, 4);
-            r -= f;
-            (*out)[((group * RB_T + rb) * 3 + s) * 512 + lane * 8 + e] = h;
-        }
+        uint16_t h[3];
+        bf16_split_host(v, 3, h);
+        for (int s = 0; s < 3; ++s) (*out)[((group * RB_T + rb) * 3 + s) * 512 + lane * 8 + e] = h[s];
     };
     for (int mblk = 0; mblk < n_mblk; ++mblk)
         for (int rb = 0; rb < RB_T; ++rb)
@@ -452,25 +416,15 @@ void upsbf_pack_host(const float *uw, const float *nw, const float *bias, int c_
             }
 }
 
-static int ub_cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
-}
-
 template <int R, int MB>
 static int ub_launch(UbParams p, int batch, hipStream_t stream) {
     using GM = UbGeom<R, MB>;
     if (reserve_whole_cu((const void *)upsbf_kernel<R, MB>, "upsbf")) return 1;
     p.col_tiles = (int)ceil_div(p.L_in + 1, GM::N1);
     p.n_tiles = p.col_tiles * p.n_mblk * batch;
-    p.per_xcd = (int)ceil_div(p.n_tiles, 8);
-    const int cus = ub_cu_count() / 8 * 8;
-    const int slots = (int)std::min<int64_t>(cus / 8, p.per_xcd);
-    hipLaunchKernelGGL((upsbf_kernel<R, MB>), dim3((unsigned)(slots * 8)), dim3(UB_NTH), LDS_WHOLE_CU, stream, p);
+    const PersistentGrid g = persistent_grid(p.n_tiles);
+    p.per_xcd = g.per_xcd;
+    hipLaunchKernelGGL((upsbf_kernel<R, MB>), dim3(g.blocks), dim3(UB_NTH), LDS_WHOLE_CU, stream, p);
     RVC_LAUNCH_CHECK();
     return 0;
 }
@@ -481,8 +435,8 @@ static int ub_launch(UbParams p, int batch, hipStream_t stream) {
 int launch_upsbf(const float *x, const float *har, int64_t Lh, const void *u, const float *bias, float *y, int batch, int c_in, int c_out,
                  int64_t L_in, int64_t L_out, int rate, int ksize, int pad, int vk, int64_t S, int64_t P, float slope, hipStream_t stream) {
     if (!upsbf_supported(c_in, c_out, rate, ksize, vk)) return fail("upsbf: unsupported shape (%d -> %d channels, rate %d, kernel %d, %d noise rows)", c_in, c_out, rate, ksize, vk);
-    if (vk > 0 && (!har || Lh <= 0 || Lh * 4 >= ((int64_t)1 << 31) || S > 4096 || P > 65536)) return fail("upsbf: bad noise source");
-    if ((int64_t)c_in * L_in * 4 >= ((int64_t)1 << 31) || (int64_t)c_out * L_out * 4 >= ((int64_t)1 << 31)) return fail("upsbf: slab exceeds the 2 GiB buffer addressing");
+    if (vk > 0 && (!har || Lh <= 0 || !fits_2gib(Lh, 4) || S > 4096 || P > 65536)) return fail("upsbf: bad noise source");
+    if (!fits_2gib((int64_t)c_in * L_in, 4) || !fits_2gib((int64_t)c_out * L_out, 4)) return fail("upsbf: slab exceeds the 2 GiB buffer addressing");
     if (L_in <= 0 || batch <= 0) return 0;
     UbParams p;
     p.x = x; p.har = har; p.u = u; p.bias = bias; p.y = y; p.L_in = L_in; p.L_out = L_out; p.Lh = vk > 0 ? Lh : 0;
@@ -524,10 +478,7 @@ extern "C" int rvc_upsample_bf16x3_pack_weight(const float *up_w_host, const flo
     const int vk = upsbf_fold_noise(nc_k) ? (rate - 1) * nc_stride + nc_k : 0;
     std::vector<uint16_t> u;
     upsbf_pack_host(up_w_host, noise_w_host, bias_host, c_in, c_out, rate, ksize, vk, nc_k, nc_stride, &u);
-    hipError_t e = hipMemcpyAsync(u_dev, u.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_upsample_bf16x3_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_upsample_bf16x3_pack_weight", u.data(), bytes, u_dev, stream);
 }
 
 extern "C" int rvc_upsample_bf16x3_forward(const float *x_dev, const float *har_dev, int64_t har_len, const void *u_dev, const float *bias_dev,

@@ -57,7 +57,6 @@ struct WinoParams {
 
 constexpr int WINO_MAX_DIL = 5;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef const void __attribute__((address_space(1))) *wino_gptr_t;
 typedef void __attribute__((address_space(3))) *wino_lptr_t;
 
@@ -79,7 +78,6 @@ __device__ __forceinline__ f32x2 lrelu2_plain(f32x2 v, float slope) {
 __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
 }
-constexpr int WINO_RSRC_FLAGS = 0x00020000;   // raw buffer, 32-bit data format
 
 // KW taps; WM x WN waves (each 32 channels x 32 tiles); CIC input channels per chunk.
 //
@@ -162,9 +160,9 @@ wino_conv_kernel(const WinoParams p) {
     // Both streams use buffer instructions: a scalar row / chunk offset plus a per-lane 32-bit offset fixed for the whole
     // block, so staging costs no address arithmetic on the vector pipe.
     __builtin_assume(wave >= 0 && wave < NW);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), WINO_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), RSRC_RAW32);
     const __amdgpu_buffer_rsrc_t urs =
-        __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)3 * G3 * (c_in / 2) * c_out * UPAIR), WINO_RSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)3 * G3 * (c_in / 2) * c_out * UPAIR), RSRC_RAW32);
     const int L4 = (int)(L * 4);
     unsigned goff[NJ];    // byte offset of the sample inside a channel row (clamped into [0, L))
     int loff[NJ];         // float2 offset inside a channel pair's 4 rows: ii * XTS + tile (lanes with nothing to stage: a pad column)
@@ -595,7 +593,7 @@ static int wino_launch_kw(const WinoParams &p, hipStream_t stream) {
 }
 
 // the staging streams address one batch item's input and the weight slab with 32-bit byte offsets
-bool wino_fits(int c_in, int c_out, int64_t L) { return (int64_t)c_in * L < ((int64_t)1 << 29) && (int64_t)12 * c_in * c_out < ((int64_t)1 << 29); }
+bool wino_fits(int c_in, int c_out, int64_t L) { return fits_2gib((int64_t)c_in * L, 4) && fits_2gib((int64_t)12 * c_in * c_out, 4); }
 
 bool wino_supported(int k, int dil) { return (k == 3 || k == 7 || k == 11) && dil >= 1 && dil <= WINO_MAX_DIL; }
 

@@ -91,24 +91,19 @@ constexpr int WBF_NW = 8, WBF_NTH = 512, WBF_CIC = 16, WBF_CP = 8, WBF_NP = 7, W
 // block shapes: 64 channels x 128 window columns (waves 2 x 4), or 128 channels x 64 columns (4 x 2) where c_out allows -- all of a
 // 128-channel layer's outputs of a time tile in ONE block, so the raw rows are staged and transformed once instead of twice
 
-typedef float wbf_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 wbf_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 wbf_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned wbf_u32x4 __attribute__((ext_vector_type(4)));
 typedef void __attribute__((address_space(3))) *wbf_lptr_t;
 
-__device__ __forceinline__ wbf_f32x2 wbf_fma2(float a, wbf_f32x2 b, wbf_f32x2 c) { return __builtin_elementwise_fma(wbf_f32x2{a, a}, b, c); }
-__device__ __forceinline__ wbf_f32x2 wbf_lrelu2(wbf_f32x2 v, float slope) {
-    const wbf_f32x2 sv = v * slope;
+__device__ __forceinline__ f32x2 wbf_fma2(float a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(f32x2{a, a}, b, c); }
+__device__ __forceinline__ f32x2 wbf_lrelu2(f32x2 v, float slope) {
+    const f32x2 sv = v * slope;
     float a, b;
     asm("v_max_f32 %0, %1, %2" : "=v"(a) : "v"(v.x), "v"(sv.x));
     asm("v_max_f32 %0, %1, %2" : "=v"(b) : "v"(v.y), "v"(sv.y));
-    return wbf_f32x2{a, b};
+    return f32x2{a, b};
 }
 __device__ __forceinline__ float wbf_buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
 }
-constexpr int WBF_RSRC_FLAGS = 0x00020000;
 
 // geometry shared by the kernel and the launcher
 template <int KW, int BM, int BNT>
@@ -155,7 +150,7 @@ winobf_conv_kernel(const WinoBfParams p) {
 
     extern __shared__ __attribute__((aligned(16))) float wbf_smem[];
     unsigned char *const smem = reinterpret_cast<unsigned char *>(wbf_smem);
-    wbf_f32x2 *const xs = reinterpret_cast<wbf_f32x2 *>(smem);                       // raw chunks [2][CP][4][XTS]
+    f32x2 *const xs = reinterpret_cast<f32x2 *>(smem);                       // raw chunks [2][CP][4][XTS]
     constexpr int XRAW = CP * 4 * XTS;                                                // float2 per raw buffer
     unsigned char *const bs = smem + 2 * GM::RAW_BYTES;                               // [2][B_SLOT]
     unsigned char *const as = bs + 2 * GM::B_SLOT;                                    // [3][A_SLOT]
@@ -187,9 +182,9 @@ winobf_conv_kernel(const WinoBfParams p) {
     const bool edge = t_start < 0 || t_start + span > L;
 
     // ---- staging plan of the raw input rows (as wino.hip: one division set per block) -----------------------------
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), WBF_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), RSRC_RAW32);
     const __amdgpu_buffer_rsrc_t urs =
-        __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)c_in * c_out * NP * G * 6), WBF_RSRC_FLAGS);
+        __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)c_in * c_out * NP * G * 6), RSRC_RAW32);
     const int L4 = (int)(L * 4);
     unsigned goff[NJ];
     int loff[NJ];
@@ -212,24 +207,24 @@ winobf_conv_kernel(const WinoBfParams p) {
     // a chunk's rows are fetched in two halves of four channel pairs (16 registers in flight instead of 32) and land in the
     // raw buffer the transforms are NOT reading (chunk c lives in buffer c & 1)
     constexpr int HP = CP / 2;
-    wbf_f32x2 xr[HP * NJ];
+    f32x2 xr[HP * NJ];
     auto load_x = [&](int c, int h) __attribute__((always_inline)) {
 #pragma unroll
         for (int cp = 0; cp < HP; ++cp) {
             const int s0 = (c * CIC + 2 * (h * HP + cp)) * L4;
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) xr[cp * NJ + j] = wbf_f32x2{wbf_buf_load(xrs, goff[j], s0), wbf_buf_load(xrs, goff[j], s0 + L4)};
+            for (int j = 0; j < NJ; ++j) xr[cp * NJ + j] = f32x2{wbf_buf_load(xrs, goff[j], s0), wbf_buf_load(xrs, goff[j], s0 + L4)};
         }
     };
     static_assert(NJ <= 2, "the zero-padding mask below holds one keep word for j = 0 and one for j = 1");
     const unsigned keep0 = (!edge || (inb & 1)) ? 0xffffffffu : 0u, keep1 = (!edge || (inb & 2)) ? 0xffffffffu : 0u;   // conv zero padding
     auto store_x1 = [&](int c, int h, int cp) __attribute__((always_inline)) {   // one channel pair of the half
-        wbf_f32x2 *const dst = xs + (c & 1) * XRAW + (h * HP + cp) * 4 * XTS;
+        f32x2 *const dst = xs + (c & 1) * XRAW + (h * HP + cp) * 4 * XTS;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            const wbf_f32x2 v = wbf_lrelu2(xr[cp * NJ + j], slope);
+            const f32x2 v = wbf_lrelu2(xr[cp * NJ + j], slope);
             const unsigned k = j == 0 ? keep0 : keep1;
-            dst[loff[j]] = wbf_f32x2{__uint_as_float(__float_as_uint(v.x) & k), __uint_as_float(__float_as_uint(v.y) & k)};
+            dst[loff[j]] = f32x2{__uint_as_float(__float_as_uint(v.x) & k), __uint_as_float(__float_as_uint(v.y) & k)};
         }
     };
     auto store_x = [&](int c, int h) __attribute__((always_inline)) {
@@ -267,12 +262,12 @@ winobf_conv_kernel(const WinoBfParams p) {
         t_src[q] = cp * 4 * XTS - MLO * d + tau;
         t_dst[q] = (cp >> 2) * (XBP * 16) + tau * 16 + (cp & 3) * 4;
     }
-    wbf_f32x2 tq[TQ][NP];          // the window samples a point needs (round q)
-    wbf_f32x2 tv[TQ];              // transformed pair, then the split residual
+    f32x2 tq[TQ][NP];          // the window samples a point needs (round q)
+    f32x2 tv[TQ];              // transformed pair, then the split residual
     unsigned tw[TQ][3];            // the three bf16 pairs
-    auto t_read = [&](auto PT, int q, const wbf_f32x2 *raw) __attribute__((always_inline)) {
+    auto t_read = [&](auto PT, int q, const f32x2 *raw) __attribute__((always_inline)) {
         constexpr int pt = decltype(PT)::value;
-        const wbf_f32x2 *const src = raw + t_src[q];
+        const f32x2 *const src = raw + t_src[q];
         constexpr int lo = pt == 0 ? 0 : 1, hi = pt == 0 ? 5 : (pt == 6 ? 6 : 5);
 #pragma unroll
         for (int n = lo; n <= hi; ++n) {
@@ -283,16 +278,16 @@ winobf_conv_kernel(const WinoBfParams p) {
     };
     auto t_xform = [&](auto PT, int q) __attribute__((always_inline)) {
         constexpr int pt = decltype(PT)::value;
-        const wbf_f32x2(&dq)[NP] = tq[q];
+        const f32x2(&dq)[NP] = tq[q];
         if constexpr (pt == 0) {
             tv[q] = wbf_fma2(-0.5f, dq[0], wbf_fma2(0.25f, dq[1], wbf_fma2(2.5f, dq[2], wbf_fma2(-1.25f, dq[3], wbf_fma2(-2.f, dq[4], dq[5])))));
         } else if constexpr (pt == 1 || pt == 2) {
-            const wbf_f32x2 A = wbf_fma2(0.5f, dq[2], wbf_fma2(-0.25f, dq[3], wbf_fma2(-2.f, dq[4], dq[5])));
-            const wbf_f32x2 B = wbf_fma2(0.5f, dq[1], wbf_fma2(-0.25f, dq[2], wbf_fma2(-2.f, dq[3], dq[4])));
+            const f32x2 A = wbf_fma2(0.5f, dq[2], wbf_fma2(-0.25f, dq[3], wbf_fma2(-2.f, dq[4], dq[5])));
+            const f32x2 B = wbf_fma2(0.5f, dq[1], wbf_fma2(-0.25f, dq[2], wbf_fma2(-2.f, dq[3], dq[4])));
             tv[q] = pt == 1 ? A + B : A - B;
         } else if constexpr (pt == 3 || pt == 4) {
-            const wbf_f32x2 A2 = wbf_fma2(2.f, dq[2], wbf_fma2(-2.f, dq[4], dq[5] - dq[3]));
-            const wbf_f32x2 B2 = wbf_fma2(-0.5f, dq[2], wbf_fma2(0.5f, dq[4], dq[1] - dq[3]));
+            const f32x2 A2 = wbf_fma2(2.f, dq[2], wbf_fma2(-2.f, dq[4], dq[5] - dq[3]));
+            const f32x2 B2 = wbf_fma2(-0.5f, dq[2], wbf_fma2(0.5f, dq[4], dq[1] - dq[3]));
             tv[q] = pt == 3 ? A2 + B2 : A2 - B2;
         } else if constexpr (pt == 5) {
             tv[q] = wbf_fma2(0.25f, dq[1], wbf_fma2(-1.25f, dq[3], dq[5]));
@@ -302,9 +297,9 @@ winobf_conv_kernel(const WinoBfParams p) {
     };
     // exact three-way split: v = v0 + v1 + v2, each a pair of bf16 (even channel in the low half)
     auto t_split = [&](int q, int level) __attribute__((always_inline)) {
-        const unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector(tv[q], wbf_bf16x2));
+        const unsigned w = split_word(tv[q]);
         tw[q][level] = w;
-        if (level < 2) tv[q] = tv[q] - wbf_f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+        if (level < 2) tv[q] = tv[q] - f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
     };
     auto t_write = [&](int q, unsigned char *const dstb) __attribute__((always_inline)) {
         unsigned char *o = dstb + t_dst[q];
@@ -331,13 +326,13 @@ winobf_conv_kernel(const WinoBfParams p) {
     // Fragment registers: the tap fragments of two groups (double-buffered), the window fragments of ONE -- the products of a
     // group are ordered so that b2 and b1 die after the first and third instruction and are reloaded for the next group while
     // the current one finishes; b0 follows after the sixth.
-    wbf_bf16x8 fa[2][3], fb[3];
+    bf16x8 fa[2][3], fb[3];
     auto f_read_a = [&](int g, const unsigned char *ab) __attribute__((always_inline)) {
 #pragma unroll
-        for (int sp = 0; sp < 3; ++sp) fa[g & 1][sp] = __builtin_bit_cast(wbf_bf16x8, *reinterpret_cast<const wbf_u32x4 *>(ab + (g * WM * 3 + sp) * 1024));
+        for (int sp = 0; sp < 3; ++sp) fa[g & 1][sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(ab + (g * WM * 3 + sp) * 1024));
     };
     auto f_read_b = [&](int g, int sp, const unsigned char *bb) __attribute__((always_inline)) {
-        fb[sp] = __builtin_bit_cast(wbf_bf16x8, *reinterpret_cast<const wbf_u32x4 *>(bb + sp * 2 * (XBP * 16) + g * d * 16));
+        fb[sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(bb + sp * 2 * (XBP * 16) + g * d * 16));
     };
 
     // ---- prologue --------------------------------------------------------------------------------------------------
@@ -374,7 +369,7 @@ winobf_conv_kernel(const WinoBfParams p) {
             unsigned char *const dstb = bs + ((s + 1) & 1) * GM::B_SLOT;
             const unsigned char *ab = as + (s % 3) * GM::A_SLOT + wm * 3 * 1024 + lane * 16;   // [g][32-channel block wm][split]
             const unsigned char *bb = bs + (s & 1) * GM::B_SLOT + b_lane;
-            const wbf_f32x2 *const raw = xs + ((pt == NP - 1 ? c + 1 : c) & 1) * XRAW;    // the chunk of step s + 1
+            const f32x2 *const raw = xs + ((pt == NP - 1 ? c + 1 : c) & 1) * XRAW;    // the chunk of step s + 1
             constexpr bool T = !(DBG & 1), M = !(DBG & 2);
             // filler stage k goes after matrix instruction k of the step
             auto filler = [&](int k) __attribute__((always_inline)) {
@@ -607,7 +602,7 @@ bool winobf_supported(int c_in, int c_out, int k, int dil) {
 }
 
 bool winobf_fits(int c_in, int c_out, int64_t L) {
-    return (int64_t)c_in * L < ((int64_t)1 << 29) && (int64_t)c_in * c_out * WBF_NP * 3 * 6 < ((int64_t)1 << 31);
+    return fits_2gib((int64_t)c_in * L, 4) && fits_2gib((int64_t)c_in * c_out * WBF_NP * 3, 6);
 }
 
 size_t winobf_weight_bytes(int c_out, int c_in, int k) { return (size_t)c_out * c_in * (k == 3 ? 6 : WBF_NP * ((k + 3) / 4)) * 3 * 2; }
@@ -658,16 +653,6 @@ void winobf_pack_host(const float *w_host, int c_out, int c_in, int k, std::vect
     const int G = (k + R - 1) / R, n_chunks = c_in / WBF_CIC, n_m = c_out / BM;
     const bool point_major = winobf_takes_v2(c_in, c_out, k);
     out->assign((size_t)c_out * c_in * NPT * G * 3, 0);
-    auto split3 = [](float v, uint16_t s[3]) {
-        float r = v;
-        for (int i = 0; i < 3; ++i) {
-            s[i] = bf16_rne(r);
-            uint32_t bits = (uint32_t)s[i] << 16;
-            float f;
-            memcpy(&f, &bits, 4);
-            r -= f;                      // exact in fp32
-        }
-    };
     for (int mb = 0; mb < n_m; ++mb)
         for (int c = 0; c < n_chunks; ++c)
             for (int pt = 0; pt < NPT; ++pt)
@@ -701,7 +686,7 @@ void winobf_pack_host(const float *w_host, int c_out, int c_in, int k, std::vect
                                     default: u = w[3]; break;
                                 }
                                 uint16_t s[3];
-                                split3((float)u, s);
+                                bf16_split_host((float)u, 3, s);
                                 // this kernel walks (chunk, point); winobf2.hip's waves each own a point and walk its chunks
                                 const size_t step = point_major ? ((size_t)mb * NPT + pt) * n_chunks + c : ((size_t)mb * n_chunks + c) * NPT + pt;
                                 for (int sp = 0; sp < 3; ++sp) {
@@ -738,10 +723,7 @@ extern "C" int rvc_conv1d_winobf_pack_weight(const float *w_host, int c_out, int
     if (rvc_conv1d_winobf_weight_bytes(c_out, c_in, k, &bytes)) return 1;
     std::vector<uint16_t> u;
     winobf_pack_host(w_host, c_out, c_in, k, &u);
-    hipError_t e = hipMemcpyAsync(u_dev, u.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) return fail("rvc_conv1d_winobf_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    return upload_packed("rvc_conv1d_winobf_pack_weight", u.data(), bytes, u_dev, stream);
 }
 
 extern "C" int rvc_conv1d_winobf_forward(const float *x_dev, const void *u_dev, const float *bias_dev, const float *res_dev,

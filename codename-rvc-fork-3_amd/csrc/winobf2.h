@@ -25,17 +25,10 @@ struct Wbf2Params {
 constexpr int W2_MAX_DIL = 5;
 constexpr int W2_NTH = 512, W2_BNT = 64, W2_CIC = 16, W2_CP = 8, W2_R = 4, W2_LOADER = 7;
 
-typedef float w2_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 w2_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 w2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned w2_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned w2_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ w2_f32x2 w2_lrelu2(w2_f32x2 v, float slope) {
-    const w2_f32x2 sv = v * slope;
-    return w2_f32x2{__builtin_fmaxf(v.x, sv.x), __builtin_fmaxf(v.y, sv.y)};
+__device__ __forceinline__ f32x2 w2_lrelu2(f32x2 v, float slope) {
+    const f32x2 sv = v * slope;
+    return f32x2{__builtin_fmaxf(v.x, sv.x), __builtin_fmaxf(v.y, sv.y)};
 }
-constexpr int W2_RSRC_FLAGS = 0x00020000;
 
 // rows of the F(4,4) input transform B^T for the points 0, 1, -1, 1/2, -1/2, 2, inf (the expressions of wino.hip / winobf.hip
 // multiplied out; every entry is exact in fp32): X_p = sum_n W2_BT[p][n] * x[n]

@@ -51,7 +51,7 @@ winobf2_conv_kernel(const Wbf2Params p) {
 
     extern __shared__ __attribute__((aligned(16))) float w2_smem[];
     unsigned char *const smem = reinterpret_cast<unsigned char *>(w2_smem);
-    w2_f32x2 *const xs = reinterpret_cast<w2_f32x2 *>(smem);              // raw chunks [2][CP][4][XTS]
+    f32x2 *const xs = reinterpret_cast<f32x2 *>(smem);              // raw chunks [2][CP][4][XTS]
     constexpr int XRAW = CP * 4 * XTS;                                     // float2 per raw buffer
     unsigned char *const bs_all = smem + 2 * GM::RAW_BYTES;                // [point][2][B_WAVE]
 
@@ -148,7 +148,7 @@ winobf2_conv_kernel(const Wbf2Params p) {
     const int64_t t_start = (sb0 + MLO) * 4 * d;
     const int span = 4 * xt_used;                                  // staged samples per row (a multiple of 4, <= 4 XT)
     const bool edge = t_start < 0 || t_start + span > L;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), W2_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)px, 0, (int)((int64_t)c_in * L * 4), RSRC_RAW32);
     const int L4 = (int)(L * 4);
     // (the row width is decided ONCE, outside everything: a runtime `wide` test around each load makes hipcc wait for every load on its own)
     auto run = [&](auto WIDE, auto EDGE) __attribute__((always_inline)) {
@@ -205,15 +205,15 @@ winobf2_conv_kernel(const Wbf2Params p) {
     };
     auto write = [&](int c, auto SET) __attribute__((always_inline)) {
         constexpr int st = decltype(SET)::value;
-        w2_f32x2 *const dst0 = xs + (c & 1) * XRAW;
+        f32x2 *const dst0 = xs + (c & 1) * XRAW;
 #pragma unroll
         for (int q = 0; q < CP; ++q) {
-            w2_f32x2 *const dst = dst0 + q * 4 * XTS;
+            f32x2 *const dst = dst0 + q * 4 * XTS;
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
                 if (wide ? k >= NS_W : k >= NS_N) continue;
-                const w2_f32x2 v = w2_lrelu2(w2_f32x2{xr[st][2 * q][k], xr[st][2 * q + 1][k]}, slope);
-                if constexpr (edge_c) dst[loff[k]] = w2_f32x2{__uint_as_float(__float_as_uint(v.x) & keep[k]), __uint_as_float(__float_as_uint(v.y) & keep[k])};
+                const f32x2 v = w2_lrelu2(f32x2{xr[st][2 * q][k], xr[st][2 * q + 1][k]}, slope);
+                if constexpr (edge_c) dst[loff[k]] = f32x2{__uint_as_float(__float_as_uint(v.x) & keep[k]), __uint_as_float(__float_as_uint(v.y) & keep[k])};
                 else dst[loff[k]] = v;
             }
         }
@@ -246,12 +246,12 @@ winobf2_conv_kernel(const Wbf2Params p) {
         }
     };
     auto pair0_write = [&](int q) __attribute__((always_inline)) {
-        w2_f32x2 *const dst = xs + q * 4 * XTS;
+        f32x2 *const dst = xs + q * 4 * XTS;
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
             if (wide ? k >= NS_W : k >= NS_N) continue;
-            const w2_f32x2 v = w2_lrelu2(w2_f32x2{r0[k], r1[k]}, slope);
-            if constexpr (edge_c) dst[loff[k]] = w2_f32x2{__uint_as_float(__float_as_uint(v.x) & keep[k]), __uint_as_float(__float_as_uint(v.y) & keep[k])};
+            const f32x2 v = w2_lrelu2(f32x2{r0[k], r1[k]}, slope);
+            if constexpr (edge_c) dst[loff[k]] = f32x2{__uint_as_float(__float_as_uint(v.x) & keep[k]), __uint_as_float(__float_as_uint(v.y) & keep[k])};
             else dst[loff[k]] = v;
         }
     };
@@ -280,34 +280,34 @@ winobf2_conv_kernel(const Wbf2Params p) {
 #pragma unroll
         for (int r = 0; r < (G > 1 ? HR : 0); ++r) {
             if (!h_on[r]) continue;
-            const w2_f32x2 *const raw = xs + (c & 1) * XRAW + h_src[r];
+            const f32x2 *const raw = xs + (c & 1) * XRAW + h_src[r];
             unsigned w[3][2];
 #pragma unroll
             for (int e2 = 0; e2 < 2; ++e2) {
-                w2_f32x2 q7[7];
+                f32x2 q7[7];
 #pragma unroll
                 for (int n = 0; n < 7; ++n) {
                     const int sh = n - C0;
                     q7[n] = raw[(e2 * 4 + (sh & 3)) * XTS + (sh >> 2) * d];
                 }
                 // the compute waves' expression, term for term (t_xform2)
-                w2_f32x2 a = q7[0] * hbt[r][0], b2 = q7[1] * hbt[r][1];
-                a = __builtin_elementwise_fma(w2_f32x2{hbt[r][2], hbt[r][2]}, q7[2], a);
-                b2 = __builtin_elementwise_fma(w2_f32x2{hbt[r][3], hbt[r][3]}, q7[3], b2);
-                a = __builtin_elementwise_fma(w2_f32x2{hbt[r][4], hbt[r][4]}, q7[4], a);
-                b2 = __builtin_elementwise_fma(w2_f32x2{hbt[r][5], hbt[r][5]}, q7[5], b2);
-                a = __builtin_elementwise_fma(w2_f32x2{hbt[r][6], hbt[r][6]}, q7[6], a);
-                w2_f32x2 v = a + b2;
+                f32x2 a = q7[0] * hbt[r][0], b2 = q7[1] * hbt[r][1];
+                a = __builtin_elementwise_fma(f32x2{hbt[r][2], hbt[r][2]}, q7[2], a);
+                b2 = __builtin_elementwise_fma(f32x2{hbt[r][3], hbt[r][3]}, q7[3], b2);
+                a = __builtin_elementwise_fma(f32x2{hbt[r][4], hbt[r][4]}, q7[4], a);
+                b2 = __builtin_elementwise_fma(f32x2{hbt[r][5], hbt[r][5]}, q7[5], b2);
+                a = __builtin_elementwise_fma(f32x2{hbt[r][6], hbt[r][6]}, q7[6], a);
+                f32x2 v = a + b2;
 #pragma unroll
                 for (int level = 0; level < 3; ++level) {
-                    const unsigned ww = __builtin_bit_cast(unsigned, __builtin_convertvector(v, w2_bf16x2));
+                    const unsigned ww = split_word(v);
                     w[level][e2] = ww;
-                    if (level < 2) v = v - w2_f32x2{__uint_as_float(ww << 16), __uint_as_float(ww & 0xffff0000u)};
+                    if (level < 2) v = v - f32x2{__uint_as_float(ww << 16), __uint_as_float(ww & 0xffff0000u)};
                 }
             }
             unsigned char *o = bs_all + (c & 1) * GM::B_WAVE + h_dst[r];
 #pragma unroll
-            for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<w2_u32x2 *>(o + sp * 2 * GM::B_PLANE) = w2_u32x2{w[sp][0], w[sp][1]};
+            for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<u32x2 *>(o + sp * 2 * GM::B_PLANE) = u32x2{w[sp][0], w[sp][1]};
         }
     };
     // (Pulling the block's residual tile into L2 from here during the last two phases -- LDS-DMA into a sink, no registers -- cut the
@@ -384,12 +384,12 @@ winobf2_conv_kernel(const Wbf2Params p) {
         // the groups (chunk, tap group, row-block pair) follow each other in the order the wave consumes them, 6 KiB apiece: one
         // running scalar offset, the six pieces at immediate offsets
         const __amdgpu_buffer_rsrc_t urs =
-            __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)c_in * c_out * NP * G * NSA * 2), W2_RSRC_FLAGS);
+            __builtin_amdgcn_make_buffer_rsrc((void *)p.u, 0, (int)((int64_t)c_in * c_out * NP * G * NSA * 2), RSRC_RAW32);
         constexpr int A_GROUP = 2 * NSA * 1024;
         const int n_groups = n_chunks * G * NPAIR;
         const int a_base = (mblk * NP + pt) * n_groups * A_GROUP;
         const int a_last = a_base + (n_groups - 1) * A_GROUP;
-        w2_bf16x8 fa[2][2][NSA];                           // [buffer][row block of the pair][split]
+        bf16x8 fa[2][2][NSA];                           // [buffer][row block of the pair][split]
         auto load_a = [&](int buf, int Q) __attribute__((always_inline)) {   // group Q of this wave's stream (clamped: the tail re-reads the last one)
             int soff = a_base + Q * A_GROUP;
             soff = soff < a_last ? soff : a_last;
@@ -397,24 +397,24 @@ winobf2_conv_kernel(const Wbf2Params p) {
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                 for (int sp = 0; sp < NSA; ++sp)
-                    fa[buf][rb][sp] = __builtin_bit_cast(w2_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + (rb * NSA + sp) * 1024, soff, 0));
+                    fa[buf][rb][sp] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(urs, 16 * lane + (rb * NSA + sp) * 1024, soff, 0));
         };
         // window fragments of one tap group: [column tile][split]; single-buffered -- the products of a group are ordered so that
         // split 2 dies first, then split 1, and each is re-read for the next group while the current one finishes
-        w2_bf16x8 fb[2][3];
+        bf16x8 fb[2][3];
         const int b_lane = half * GM::B_PLANE + l31 * 16;
         auto read_b = [&](int c, int g, int sp) __attribute__((always_inline)) {
             const unsigned char *bb = bs + (c & 1) * GM::B_WAVE + sp * 2 * GM::B_PLANE + b_lane + g * d * 16;
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) fb[cb][sp] = __builtin_bit_cast(w2_bf16x8, *reinterpret_cast<const w2_u32x4 *>(bb + cb * 32 * 16));
+            for (int cb = 0; cb < 2; ++cb) fb[cb][sp] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(bb + cb * 32 * 16));
         };
         // ---- input transform of chunk c for this point: lane = window, unit u = channel pairs 2u, 2u + 1 -------------------
         const int t_src = -MLO * d + lane;                 // raw tile of the window's own super-block
-        w2_f32x2 tq[2][NP];
-        w2_f32x2 tv[2];
+        f32x2 tq[2][NP];
+        f32x2 tv[2];
         unsigned tw[3][2];
         auto t_read = [&](int c, int u) __attribute__((always_inline)) {
-            const w2_f32x2 *const raw = xs + (c & 1) * XRAW + t_src;
+            const f32x2 *const raw = xs + (c & 1) * XRAW + t_src;
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -427,24 +427,24 @@ winobf2_conv_kernel(const Wbf2Params p) {
         auto t_xform2 = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                w2_f32x2 a = tq[e][0] * bt[0], b2 = tq[e][1] * bt[1];
-                a = __builtin_elementwise_fma(w2_f32x2{bt[2], bt[2]}, tq[e][2], a);
-                b2 = __builtin_elementwise_fma(w2_f32x2{bt[3], bt[3]}, tq[e][3], b2);
-                a = __builtin_elementwise_fma(w2_f32x2{bt[4], bt[4]}, tq[e][4], a);
-                b2 = __builtin_elementwise_fma(w2_f32x2{bt[5], bt[5]}, tq[e][5], b2);
-                if constexpr (NP == 7) a = __builtin_elementwise_fma(w2_f32x2{bt[6], bt[6]}, tq[e][6], a);
+                f32x2 a = tq[e][0] * bt[0], b2 = tq[e][1] * bt[1];
+                a = __builtin_elementwise_fma(f32x2{bt[2], bt[2]}, tq[e][2], a);
+                b2 = __builtin_elementwise_fma(f32x2{bt[3], bt[3]}, tq[e][3], b2);
+                a = __builtin_elementwise_fma(f32x2{bt[4], bt[4]}, tq[e][4], a);
+                b2 = __builtin_elementwise_fma(f32x2{bt[5], bt[5]}, tq[e][5], b2);
+                if constexpr (NP == 7) a = __builtin_elementwise_fma(f32x2{bt[6], bt[6]}, tq[e][6], a);
                 tv[e] = a + b2;
             }
         };
         auto t_split = [&](int e, int level) __attribute__((always_inline)) {
-            const unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector(tv[e], w2_bf16x2));
+            const unsigned w = split_word(tv[e]);
             tw[level][e] = w;
-            if (level < 2) tv[e] = tv[e] - w2_f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+            if (level < 2) tv[e] = tv[e] - f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
         };
         auto t_write = [&](int c, int u) __attribute__((always_inline)) {
             unsigned char *o = bs + (c & 1) * GM::B_WAVE + (u >> 1) * GM::B_PLANE + lane * 16 + (u & 1) * 8;
 #pragma unroll
-            for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<w2_u32x2 *>(o + sp * 2 * GM::B_PLANE) = w2_u32x2{tw[sp][0], tw[sp][1]};
+            for (int sp = 0; sp < 3; ++sp) *reinterpret_cast<u32x2 *>(o + sp * 2 * GM::B_PLANE) = u32x2{tw[sp][0], tw[sp][1]};
         };
         auto transform_unit = [&](int c, int u) __attribute__((always_inline)) {
             t_read(c, u);
@@ -754,7 +754,7 @@ bool winobf2_supported(int c_in, int c_out, int k, int dil) {
 }
 
 bool winobf2_fits(int c_in, int c_out, int64_t L) {
-    return (int64_t)c_in * L < ((int64_t)1 << 29) && (int64_t)c_in * c_out * 7 * 3 * 6 < ((int64_t)1 << 31);
+    return fits_2gib((int64_t)c_in * L, 4) && fits_2gib((int64_t)c_in * c_out * 7 * 3, 6);
 }
 
 int launch_winobf2_conv(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch,

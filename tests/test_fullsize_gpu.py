@@ -311,9 +311,9 @@ def test_decoder_T3198_stage_by_stage_vs_oracle(S, oracle_farm, case):
 
 
 @pytest.mark.parametrize("cfg", [2, 4, 5])
-def test_convert_batch_full_length_inflight2_equals_sequential(S, hubert, monkeypatch, cfg):
+def test_convert_batch_full_length_inflight3_equals_sequential(S, hubert, monkeypatch, cfg):
     """The benchmarked MODE at the benchmarked LENGTH, for every vocoder bench.py runs that way: four 30 s utterances through
-    convert_batch with THREE in flight (bench.py's default since round 6; rounds 2-5: two, hence the name) against the same four
+    convert_batch with THREE in flight (bench.py's default since round 6; rounds 2-5: two) against the same four
     converted one at a time -- cfg 2 (48 k NSF vocoder), cfg 4 (MRF vocoder, bf16 weight storage: K3f with one-term taps next to K3y)
     and cfg 5 (RefineGAN: since round 6 its narrow (conv, conv) pairs run K3f too, so wino_conv_kernel -- the fp32 kernel that
     profiles/r05_mfma_cohabitation.txt shows returning wrong words next to a co-resident bf16-matrix workgroup -- is on no default path;
