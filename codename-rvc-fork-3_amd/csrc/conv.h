@@ -38,6 +38,7 @@ struct ConvParams {
     float out_scale = 1.f;
     int batch = 1;
     const uint32_t *w_wino16 = nullptr;   // ... stored as bf16 pairs (with w16)
+    const void *w_f16x2 = nullptr;   // fp32 taps as fp16 (hi, lo 2^11) direct-form fragments (convh2.hip, K3h; a handle in arithmetic mode 1): taken first where it applies
     const void *w_direct1 = nullptr; // bf16-VALUED taps as one-term direct-form fragments (convbf1.hip, K3d): taken first where it applies
     const void *w_winobf = nullptr;  // the transformed taps as bf16x3 matrix-instruction fragments (winobf.hip): taken next
     const float *w_wino = nullptr;   // the same taps in wino.hip's layout: launch_conv may take the fast (Winograd) form for
@@ -83,6 +84,17 @@ size_t convbf1_weight_bytes(int c, int k);
 void convbf1_pack_host(const float *w, int c, int k, std::vector<uint16_t> *out);   // w: [c][c][k], rounded to bf16 here
 int launch_convbf1(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch, int c,
                    int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
+
+// one square conv with fp32 taps in direct form on the fp16 matrix cores, taps and activations as error-corrected fp16 pairs
+// (convh2.hip, K3h): C = 128 / 256; K3d's contract (y must not alias x), ~2^-22 per product instead of exact
+bool convh2_supported(int c, int k, int dil);
+bool convh2_preferred(int c, int k);        // the layers of a mode-1 handle that take it (measured against the exact path)
+bool convh2_fits(int c, int64_t L);
+size_t convh2_weight_bytes(int c, int k);
+// w: [c][c][k]; returns non-zero WITHOUT setting the error when a tap is non-finite or |w| > 65504 (the pair cannot hold it)
+int convh2_pack_host(const float *w, int c, int k, std::vector<uint16_t> *out);
+int launch_convh2(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch, int c,
+                  int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
 
 // the upsampling step (ConvTranspose1d in polyphase form + the folded noise conv) on the bf16 matrix cores, exact bf16x3 operands
 // (upsbf.hip, K3u); even rates 2 / 8 / 10 / 12, c_in % 64 == 0, at most 64 folded noise rows

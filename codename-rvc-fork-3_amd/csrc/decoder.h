@@ -47,6 +47,7 @@ struct ConvW {
     DevBuf16 wu16;                // ... as bf16 pairs when the handle stores bf16 (two uint16 per word)
     DevBuf16 wx;                  // square 7 / 11-tap layers at >= 64 channels (fp32 storage): transformed taps split in three bf16 (winobf.hip)
     DevBuf16 wd;                  // bf16 storage, 128 / 256 channels where the fused pair does not apply: one-term direct-form fragments (convbf1.hip)
+    DevBuf16 wh;                  // arithmetic mode 1, square 128 / 256 channels where K3h is the faster kernel: fp16 (hi, lo 2^11) fragments (convh2.hip)
     int c_in = 0, c_out = 0, k = 0;
 };
 
@@ -101,6 +102,7 @@ struct rvc_decoder {
     rvc_decoder_config cfg;
     std::map<std::string, rvc::HostTensor> host;
     bool finalized = false;
+    int arithmetic = 0;       // rvc_decoder_set_arithmetic: 0 exact, 1 fp16 pairs on the layers K3h takes
     int upp = 1;
     int dim = 1;              // sine components (NSF 1, MRF 9)
     float lin_w[rvc::MRF_MAX_DIM] = {0};

@@ -473,6 +473,12 @@ int build_conv(const rvc_decoder *d, const std::string &prefix, int c_out, int c
         } else {
             wino_pack_host(w->data.data(), c_out, c_in, k, &packed);
             if (out->wu.upload(packed)) return 1;
+            // arithmetic mode 1: the fp16-pair fragments (K3h), taken before every other form; a tap tensor the pair cannot hold
+            // (non-finite, |w| > 65504) keeps its layer on the exact path
+            if (d->arithmetic == 1 && convh2_supported(c_out, k, 1) && convh2_preferred(c_out, k)) {
+                std::vector<uint16_t> frags;
+                if (!convh2_pack_host(w->data.data(), c_out, k, &frags) && out->wh.upload(frags)) return 1;
+            }
             if (winobf_enabled() && winobf_supported(c_in, c_out, k, 1)) {   // third copy: the bf16-matrix-core form's fragments
                 std::vector<uint16_t> frags;
                 winobf_pack_host(w->data.data(), c_out, c_in, k, &frags);
@@ -516,6 +522,16 @@ extern "C" int rvc_decoder_create(const rvc_decoder_config *cfg, rvc_decoder **o
     if (d->upp > 1024) { delete d; return fail("rvc_decoder_create: prod(upsample_rates) > 1024"); }
     d->dim = cfg->kind == RVC_DEC_MRF ? 9 : 1;
     *out = d;
+    return 0;
+}
+
+extern "C" int rvc_decoder_set_arithmetic(rvc_decoder *dec, int mode) {
+    if (!dec) return fail("rvc_decoder_set_arithmetic: null decoder");
+    if (mode != 0 && mode != 1) return fail("rvc_decoder_set_arithmetic: mode must be 0 (exact) or 1 (fp16 pairs), got %d", mode);
+    if (dec->finalized) return fail("rvc_decoder_set_arithmetic: decoder already finalized (the tap slabs are packed at finalize)");
+    if (mode == 1 && dec->cfg.weight_storage == 1)
+        return fail("rvc_decoder_set_arithmetic: fp16 pairs are for fp32 taps; a weight_storage = 1 handle's bf16 taps already cost three products");
+    dec->arithmetic = mode;
     return 0;
 }
 
@@ -946,7 +962,10 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
                 if (par) RVC_HIP(hipEventRecord(lanes->last[r], stream));
                 return 0;
             };
-            if (s.pair[m * nd].p && resblock_bf_fits(s.c_out, len)) {
+            // arithmetic mode 1: a branch whose convs all carry fp16-pair fragments runs them (K3h, through launch_conv) instead of the pair
+            bool f16_branch = true;
+            for (int j = 0; j < nd; ++j) f16_branch = f16_branch && s.c1[m * nd + j].wh.p && s.c2[m * nd + j].wh.p;
+            if (s.pair[m * nd].p && !f16_branch && resblock_bf_fits(s.c_out, len)) {
                 // 32- / 64-channel stages: one launch per (dilated conv, conv) pair on the bf16 matrix cores (resblock_bf.hip); blocks
                 // read their neighbours' columns, so the outputs ping-pong between Y and T1
                 for (int j = 0; j < nd; ++j) {
@@ -985,14 +1004,14 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
                 const int dil = c.res_dilations[j];
                 ConvParams p;
                 p.x1 = xin; p.c1 = s.c_out; p.slope1 = 0.1f; p.x1_bstride = bs; p.l_in = len;
-                p.w = s.c1[m * nd + j].w.p; p.w16 = s.c1[m * nd + j].w16.p; p.bias = s.c1[m * nd + j].b.p; p.w_wino = s.c1[m * nd + j].wu.p; p.w_winobf = s.c1[m * nd + j].wx.p; p.w_direct1 = s.c1[m * nd + j].wd.p;
+                p.w = s.c1[m * nd + j].w.p; p.w16 = s.c1[m * nd + j].w16.p; p.bias = s.c1[m * nd + j].b.p; p.w_wino = s.c1[m * nd + j].wu.p; p.w_winobf = s.c1[m * nd + j].wx.p; p.w_direct1 = s.c1[m * nd + j].wd.p; p.w_f16x2 = s.c1[m * nd + j].wh.p;
                 p.w_wino16 = reinterpret_cast<const uint32_t *>(s.c1[m * nd + j].wu16.p);
                 p.y = T1; p.y_bstride = bs; p.m_total = s.c_out; p.c_out = s.c_out; p.n_cols = len; p.l_out = len;
                 p.kw = k; p.dil = dil; p.padl = (k - 1) / 2 * dil; p.batch = batch;
                 if (launch_conv(p, stream)) return 1;
                 ConvParams q;
                 q.x1 = T1; q.c1 = s.c_out; q.slope1 = 0.1f; q.x1_bstride = bs; q.l_in = len;
-                q.w = s.c2[m * nd + j].w.p; q.w16 = s.c2[m * nd + j].w16.p; q.bias = s.c2[m * nd + j].b.p; q.w_wino = s.c2[m * nd + j].wu.p; q.w_winobf = s.c2[m * nd + j].wx.p; q.w_direct1 = s.c2[m * nd + j].wd.p;
+                q.w = s.c2[m * nd + j].w.p; q.w16 = s.c2[m * nd + j].w16.p; q.bias = s.c2[m * nd + j].b.p; q.w_wino = s.c2[m * nd + j].wu.p; q.w_winobf = s.c2[m * nd + j].wx.p; q.w_direct1 = s.c2[m * nd + j].wd.p; q.w_f16x2 = s.c2[m * nd + j].wh.p;
                 q.w_wino16 = reinterpret_cast<const uint32_t *>(s.c2[m * nd + j].wu16.p);
                 q.res = xin;
                 q.y_bstride = bs; q.m_total = s.c_out; q.c_out = s.c_out; q.n_cols = len; q.l_out = len;

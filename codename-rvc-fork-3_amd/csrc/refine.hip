@@ -424,7 +424,9 @@ int refine_forward(rvc_decoder *d, const float *z_dev, const float *f0_dev, cons
             RVC_LAUNCH_CHECK();
             nz += (size_t)batch * bs;
             const float *xin = A;
-            const bool pairs = s.pair[m * nd].p && resblock_bf_fits(s.ch_out, lo) && nd % 2 == 1;
+            bool f16_branch = true;   // arithmetic mode 1: every conv of the branch carries fp16-pair fragments (K3h, through launch_conv)
+            for (int j = 0; j < nd; ++j) f16_branch = f16_branch && s.c1[m * nd + j].wh.p && s.c2[m * nd + j].wh.p;
+            const bool pairs = s.pair[m * nd].p && !f16_branch && resblock_bf_fits(s.ch_out, lo) && nd % 2 == 1;
             for (int j = 0; pairs && j < nd; ++j) {   // A -> Y -> T1 -> Y ... (no in-place: blocks read neighbours' columns; an odd count ends in Y)
                 float *yout = (j % 2 == 1) ? T1 : Y;
                 if (launch_resblock_bf(xin, s.pair[m * nd + j].p, s.c1[m * nd + j].b.p, s.c2[m * nd + j].b.p, nullptr, yout, batch, s.ch_out, lo,
@@ -432,7 +434,7 @@ int refine_forward(rvc_decoder *d, const float *z_dev, const float *f0_dev, cons
                     return 1;
                 xin = yout;
             }
-            const bool fused = !pairs && resblock_layer_supported(s.ch_out, k) && nd == 3;
+            const bool fused = !pairs && !f16_branch && resblock_layer_supported(s.ch_out, k) && nd == 3;
             for (int j = 0; fused && j < nd; ++j) {   // A -> Y -> T1 -> Y (no in-place: blocks read neighbours' columns)
                 float *yout = (j == 1) ? T1 : Y;
                 if (launch_resblock_layer(xin, s.c1[m * nd + j].w.p, s.c1[m * nd + j].b.p, s.c2[m * nd + j].w.p, s.c2[m * nd + j].b.p,
@@ -444,13 +446,13 @@ int refine_forward(rvc_decoder *d, const float *z_dev, const float *f0_dev, cons
                 const int dil = c.res_dilations[j];
                 ConvParams p;
                 p.x1 = xin; p.c1 = s.ch_out; p.slope1 = slope; p.x1_bstride = bs; p.l_in = lo;
-                p.w = s.c1[m * nd + j].w.p; p.bias = s.c1[m * nd + j].b.p; p.w_wino = s.c1[m * nd + j].wu.p; p.w_winobf = s.c1[m * nd + j].wx.p;
+                p.w = s.c1[m * nd + j].w.p; p.bias = s.c1[m * nd + j].b.p; p.w_wino = s.c1[m * nd + j].wu.p; p.w_winobf = s.c1[m * nd + j].wx.p; p.w_f16x2 = s.c1[m * nd + j].wh.p;
                 p.y = T1; p.y_bstride = bs; p.m_total = s.ch_out; p.c_out = s.ch_out; p.n_cols = lo; p.l_out = lo;
                 p.kw = k; p.dil = dil; p.padl = (k - 1) / 2 * dil; p.batch = batch;
                 if (launch_conv(p, stream)) return 1;
                 ConvParams q;
                 q.x1 = T1; q.c1 = s.ch_out; q.slope1 = slope; q.x1_bstride = bs; q.l_in = lo;
-                q.w = s.c2[m * nd + j].w.p; q.bias = s.c2[m * nd + j].b.p; q.w_wino = s.c2[m * nd + j].wu.p; q.w_winobf = s.c2[m * nd + j].wx.p;
+                q.w = s.c2[m * nd + j].w.p; q.bias = s.c2[m * nd + j].b.p; q.w_wino = s.c2[m * nd + j].wu.p; q.w_winobf = s.c2[m * nd + j].wx.p; q.w_f16x2 = s.c2[m * nd + j].wh.p;
                 q.res = xin; q.y = Y;
                 q.y_bstride = bs; q.m_total = s.ch_out; q.c_out = s.ch_out; q.n_cols = lo; q.l_out = lo;
                 q.kw = k; q.dil = 1; q.padl = (k - 1) / 2; q.batch = batch;

@@ -126,6 +126,11 @@ SYMBOLS = {
     "rvc_upsample_bf16x3_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rvc_upsample_bf16x3_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "rvc_conv1d_f16x2_weight_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "rvc_conv1d_f16x2_pack_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "rvc_conv1d_f16x2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int,
+                                         c_int, c_float, c_float, c_void_p]),
+    "rvc_decoder_set_arithmetic": (c_int, [c_void_p, c_int]),
     "rvc_conv1d_bf16w_weight_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "rvc_conv1d_bf16w_pack_weight": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "rvc_conv1d_bf16w_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int,
@@ -683,6 +688,35 @@ def conv1d_bf16w_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=Non
     return y
 
 
+# ---- K3h: one square conv with fp32 taps on error-corrected fp16 pairs, direct form (C = 128 / 256) ---------------
+def conv1d_f16x2_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
+    """nn.Conv1d weight [c, c, k] -> fp16 (hi, lo * 2^11) direct-form fragment slab on the device; raises for a tap that is
+    non-finite or beyond +-65504."""
+    w = w.detach().float().cpu().contiguous()
+    c, c_in, k = w.shape
+    if c != c_in:
+        raise NativeError(f"conv1d_f16x2: a square conv expected, got {tuple(w.shape)}")
+    n = c_size_t()
+    _check(_lib.rvc_conv1d_f16x2_weight_bytes(c, k, ctypes.byref(n)), "rvc_conv1d_f16x2_weight_bytes")
+    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
+    _check(_lib.rvc_conv1d_f16x2_pack_weight(w.data_ptr(), c, k, u.data_ptr(), _stream()), "rvc_conv1d_f16x2_pack_weight")
+    return u
+
+
+def conv1d_f16x2_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
+    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3h)."""
+    x = _dev_f32(x, "x")
+    b, c, length = x.shape
+    y = out if out is not None else torch.empty_like(x)
+    if y.data_ptr() == x.data_ptr():
+        raise NativeError("conv1d_f16x2: x and y must not alias")
+    _check(_lib.rvc_conv1d_f16x2_forward(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                         res.data_ptr() if res is not None else None, acc.data_ptr() if acc is not None else None,
+                                         y.data_ptr(), b, c, length, k, dilation, float(slope_in), float(out_scale), _stream()),
+           "rvc_conv1d_f16x2_forward")
+    return y
+
+
 # ---- K3u: upsampling step (polyphase ConvTranspose1d + folded noise conv) on the bf16 matrix cores -----------------
 def upsample_bf16x3_pack_weight(up_w: torch.Tensor, noise_w, bias, rate: int, nc_stride: int, device):
     """ConvTranspose1d weight [c_in, c_out, ksize] (+ the noise conv's weight [c_out, 1, nc_k] or None, + the summed bias [c_out] or None)
@@ -947,6 +981,7 @@ def conv2d_bf16x3_forward(x, u, bias, c_out, relu=False, res=None, out=None):
 
 # ---- K2/K3 -----------------------------------------------------------------------------------------
 DEC_KINDS = {"HiFi-GAN": 0, "MRF HiFi-GAN": 1, "RefineGAN": 2}
+DEC_ARITHMETIC = {"exact": 0, "fp16x2": 1}
 
 
 class Decoder:
@@ -954,9 +989,14 @@ class Decoder:
 
     def __init__(self, vocoder: str, sr: int, folded_weights: dict, *, in_channels=192, upsample_initial_channel=512,
                  gin_channels=256, upsample_rates=(12, 10, 2, 2), upsample_kernel_sizes=(24, 20, 4, 4),
-                 res_kernel_sizes=(3, 7, 11), res_dilations=(1, 3, 5), weight_storage: str = "f32"):
+                 res_kernel_sizes=(3, 7, 11), res_dilations=(1, 3, 5), weight_storage: str = "f32",
+                 arithmetic: str = "exact"):
+        """arithmetic: "exact" (default), or "fp16x2" -- the square 128- / 256-channel ResBlock convs on error-corrected fp16
+        pairs (K3h): the fp32 result to ~2^-22 per product, faster; not with weight_storage="bf16"."""
         if not torch.cuda.is_available():
             raise NativeError("rvc_amd.Decoder needs a HIP device (no CPU fallback)")
+        if arithmetic not in DEC_ARITHMETIC:
+            raise NativeError(f"rvc_amd.Decoder: arithmetic must be one of {sorted(DEC_ARITHMETIC)}, got {arithmetic!r}")
         cfg = DecoderConfig()
         cfg.kind = DEC_KINDS[vocoder]
         cfg.sample_rate = sr
@@ -977,6 +1017,9 @@ class Decoder:
         self._h = c_void_p()
         self.vocoder = vocoder
         _check(_lib.rvc_decoder_create(ctypes.byref(cfg), ctypes.byref(self._h)), "rvc_decoder_create")
+        self.arithmetic = arithmetic
+        if arithmetic != "exact":   # (the default handle makes exactly the calls it always made)
+            _check(_lib.rvc_decoder_set_arithmetic(self._h, DEC_ARITHMETIC[arithmetic]), "rvc_decoder_set_arithmetic")
         for name, t in folded_weights.items():
             t = t.detach().float().cpu().contiguous()
             shape = (c_int64 * t.dim())(*t.shape)

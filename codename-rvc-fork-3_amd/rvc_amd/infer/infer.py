@@ -46,6 +46,7 @@ class VoiceConverter:
         self.use_f0 = None
         self.loaded_model = None
         self.dec_weight_dtype = "f32"   # "bf16": the vocoder's conv weights are stored as bf16 in HBM (BASELINE cfg 4)
+        self.dec_arithmetic = "exact"   # "fp16x2": the vocoder's 128- / 256-channel ResBlock convs on error-corrected fp16 pairs (faster, ~2^-22 per product); not with dec_weight_dtype = "bf16"
         self.branch_streams = 0         # Decoder.set_branch_parallel for convert_batch: 0 = every vocoder launch on the utterance's stream, -1 = one side stream per ResBlock branch
 
     # ---- embedder (infer.py:64-74; file layout rvc/lib/utils.py:96-146) ----
@@ -92,6 +93,7 @@ class VoiceConverter:
                                      text_enc_hidden_dim=self.text_enc_hidden_dim, vocoder=self.vocoder)
             del self.net_g.enc_q
             self.net_g.dec_weight_dtype = self.dec_weight_dtype
+            self.net_g.dec_arithmetic = self.dec_arithmetic
             self.net_g.load_state_dict(self.cpt["weight"], strict=False)
             self.net_g = self.net_g.to(self.config.device).float()
             self.net_g.eval()

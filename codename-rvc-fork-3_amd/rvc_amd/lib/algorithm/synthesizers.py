@@ -52,6 +52,7 @@ class Synthesizer:
         self._dec_weights: Optional[Dict[str, torch.Tensor]] = None
         self.dec = None
         self.dec_weight_dtype = "f32"   # "bf16": BASELINE cfg 4, the vocoder's weights are bf16 values
+        self.dec_arithmetic = "exact"   # "fp16x2": the opt-in fast-fp32 vocoder (_native.Decoder's `arithmetic`); not with bf16 weights
 
     # ---- nn.Module-like surface used by the reference's loader ----
     def load_state_dict(self, state_dict, strict: bool = False):
@@ -80,7 +81,8 @@ class Synthesizer:
                                            gin_channels=self.gin_channels, upsample_rates=self.upsample_rates,
                                            upsample_kernel_sizes=self.upsample_kernel_sizes,
                                            res_kernel_sizes=self.resblock_kernel_sizes,
-                                           res_dilations=self.resblock_dilations, weight_storage=self.dec_weight_dtype)
+                                           res_dilations=self.resblock_dilations, weight_storage=self.dec_weight_dtype,
+                                           arithmetic=self.dec_arithmetic)
 
     def to(self, device):
         device = torch.device(device)

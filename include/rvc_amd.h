@@ -287,6 +287,16 @@ int rvc_decoder_set_concurrency_hint(rvc_decoder *dec, int utterances_in_flight)
  * Changes the workspace size (every stream owns two ping-pong buffers): query rvc_decoder_workspace_bytes afterwards. */
 int rvc_decoder_set_branch_parallel(rvc_decoder *dec, int side_streams);
 
+/* The arithmetic of the square 128- / 256-channel ResBlock / MRF-layer convs of this handle.  Call between rvc_decoder_create and
+ * rvc_decoder_finalize (refused afterwards: the tap slabs are packed at finalize).
+ *   0 (default): exact -- fp32 operands as exact bf16 triples, six matrix products per multiply-add (K3y / K3f); nothing changes.
+ *   1: error-corrected fp16 pairs (K3h, rvc_conv1d_f16x2_forward below): three matrix products per multiply-add, the fp32 result
+ *      to ~2^-22 relative per product instead of exactly; a layer whose taps the pair cannot hold (|w| > 65504, non-finite) and
+ *      every layer K3h is not the faster kernel for stay on the exact path.  Upsamplers, non-square convs and the 32- / 64-channel
+ *      stages are untouched.
+ * Refused for any other mode and on a handle created with weight_storage = 1 (its taps already cost three products). */
+int rvc_decoder_set_arithmetic(rvc_decoder *dec, int mode);
+
 /* Debug hook for the parity tests: after stage `stage` of the next forward calls, copy that stage's output
  * ([batch][C_stage][L_stage], the mean of the three ResBlocks) to tap_dev; stage -1 = har_source [batch][T*upp].
  * tap_dev = NULL switches it off. */
@@ -426,6 +436,25 @@ int rvc_resblock_bf16w_forward(const float *x_dev, const void *u_dev, const floa
 int rvc_conv1d_bf16w_weight_bytes(int c, int k, size_t *bytes);
 int rvc_conv1d_bf16w_pack_weight(const float *w_host, int c, int k, void *u_dev, void *stream);
 int rvc_conv1d_bf16w_forward(const float *x_dev, const void *u_dev, const float *bias_dev, const float *res_dev,
+                             const float *acc_dev, float *y_dev, int batch, int c, int64_t length, int k, int dilation,
+                             float slope_in, float out_scale, void *stream);
+/* ---- K3h: ONE square conv with fp32 taps on error-corrected fp16 PAIRS (the opt-in fast-fp32 vocoder mode) --------------------- *
+ * Replaces one conv of the ResBlock / MRFLayer body (rvc/lib/algorithm/residuals.py:75-86, hifigan_mrf.py:13-83) at C = 128 / 256,
+ * K = 3, 7, 11 in a decoder handle with rvc_decoder_set_arithmetic(dec, 1):
+ *     y = out_scale * (conv_d(leaky(x, slope)) + bias [+ res] [+ acc])
+ * Ootomo & Yokota's split: v -> (hi = fp16(v), lo = fp16((v - hi) 2^11)), w x ~= w_hi x_hi + 2^-11 (w_hi x_lo + w_lo x_hi): three fp16
+ * matrix products per multiply-add, two fp32 accumulators per tile (the cross terms share the 2^11 scale) combined before the bias;
+ * the dropped w_lo x_lo term is ~2^-22 of the product.  Measured relative RMS against float64: 1.5e-7 .. 3.5e-7 at activation
+ * amplitudes 1e-3 .. 1e3, the level of F.conv1d in fp32 (profiles/fastfp32_conv_shapes.txt).  fp16 subnormals contribute (the
+ * conversions and the matrix instruction keep them); below |x| ~ 6e-5 the hi part itself is subnormal and the error grows.  Activations are clamped to +-65504 after
+ * the leaky ReLU (finite, less accurate results beyond; a NaN activation counts as -65504); pack_weight REFUSES taps with |w| > 65504
+ * or a non-finite value.  Bit-reproducible from launch to launch.
+ * u_dev: rvc_conv1d_f16x2_weight_bytes() = (C / 16) K (C / 32) 2048 bytes: per (64-channel chunk, tap, 16 input channels, 32 output
+ * channels) one 1 KiB fragment of w_hi and one of w_lo 2^11.  Persistent 8-wave workgroups that own their CU (csrc/convh2.hip).
+ * dilation 1..5, leaky slope in [0, 1], C * L * 4 < 2^31; y must not alias x (res and acc may alias y). */
+int rvc_conv1d_f16x2_weight_bytes(int c, int k, size_t *bytes);
+int rvc_conv1d_f16x2_pack_weight(const float *w_host, int c, int k, void *u_dev, void *stream);
+int rvc_conv1d_f16x2_forward(const float *x_dev, const void *u_dev, const float *bias_dev, const float *res_dev,
                              const float *acc_dev, float *y_dev, int batch, int c, int64_t length, int k, int dilation,
                              float slope_in, float out_scale, void *stream);
 /* ---- K3u: the vocoder's upsampling step on the bf16 matrix cores (exact bf16x3 operands) -------------------------------------- *
