@@ -38,7 +38,7 @@ struct ConvParams {
     float out_scale = 1.f;
     int batch = 1;
     const uint32_t *w_wino16 = nullptr;   // ... stored as bf16 pairs (with w16)
-    const void *w_f16x2 = nullptr;   // fp32 taps as fp16 (hi, lo 2^11) direct-form fragments (convh2.hip, K3h; a handle in arithmetic mode 1): taken first where it applies
+    const void *w_f16x2 = nullptr;   // fp32 taps as fp16 (hi, lo 2^11) direct-form fragments (convbf1.hip, K3h; a handle in arithmetic mode 1): taken first where it applies
     const void *w_direct1 = nullptr; // bf16-VALUED taps as one-term direct-form fragments (convbf1.hip, K3d): taken first where it applies
     const void *w_winobf = nullptr;  // the transformed taps as bf16x3 matrix-instruction fragments (winobf.hip): taken next
     const float *w_wino = nullptr;   // the same taps in wino.hip's layout: launch_conv may take the fast (Winograd) form for
@@ -75,26 +75,21 @@ void resblock_bf_pack_host(const float *w1, const float *w2, int c, int k, std::
 int launch_resblock_bf(const float *x, const void *u, const float *b1, const float *b2, const float *accin, float *y, int batch, int c,
                        int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream, int tap_splits = 3);
 
-// one square conv with bf16-VALUED taps in direct form on the bf16 matrix cores, one-term taps x exact bf16x3 activations (convbf1.hip,
-// K3d): C = 128 / 256; same semantics as launch_winobf2_conv (y must not alias x)
+// one square conv in direct form on the matrix cores, C = 128 / 256 (convbf1.hip: one kernel template, two operand formats); same
+// semantics as launch_winobf2_conv (y must not alias x)
+enum Cb1Format {
+    CB1_BF16W = 0,   // K3d: bf16-VALUED taps (rounded to bf16 by the packer), one-term taps x exact bf16x3 activations
+    CB1_F16X2 = 1,   // K3h: fp32 taps, taps and activations as error-corrected fp16 pairs: ~2^-22 per product instead of exact
+};
 bool convbf1_supported(int c, int k, int dil);
-bool convbf1_preferred(int c, int k);       // the layers of a bf16-storage handle that take it (measured): the ones K3f cannot hold
+bool convbf1_preferred(Cb1Format fmt, int c, int k);   // the layers of a bf16-storage (the ones K3f cannot hold) / mode-1 handle that take it (measured)
 bool convbf1_fits(int c, int64_t L);
-size_t convbf1_weight_bytes(int c, int k);
-void convbf1_pack_host(const float *w, int c, int k, std::vector<uint16_t> *out);   // w: [c][c][k], rounded to bf16 here
-int launch_convbf1(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch, int c,
-                   int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
-
-// one square conv with fp32 taps in direct form on the fp16 matrix cores, taps and activations as error-corrected fp16 pairs
-// (convh2.hip, K3h): C = 128 / 256; K3d's contract (y must not alias x), ~2^-22 per product instead of exact
-bool convh2_supported(int c, int k, int dil);
-bool convh2_preferred(int c, int k);        // the layers of a mode-1 handle that take it (measured against the exact path)
-bool convh2_fits(int c, int64_t L);
-size_t convh2_weight_bytes(int c, int k);
-// w: [c][c][k]; returns non-zero WITHOUT setting the error when a tap is non-finite or |w| > 65504 (the pair cannot hold it)
-int convh2_pack_host(const float *w, int c, int k, std::vector<uint16_t> *out);
-int launch_convh2(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch, int c,
-                  int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
+size_t convbf1_weight_bytes(Cb1Format fmt, int c, int k);
+// w: [c][c][k]; CB1_F16X2 returns non-zero WITHOUT setting the error when a tap is non-finite or |w| > 65504 (the pair cannot hold it),
+// CB1_BF16W always packs
+int convbf1_pack_host(Cb1Format fmt, const float *w, int c, int k, std::vector<uint16_t> *out);
+int launch_convbf1(Cb1Format fmt, const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch,
+                   int c, int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
 
 // the upsampling step (ConvTranspose1d in polyphase form + the folded noise conv) on the bf16 matrix cores, exact bf16x3 operands
 // (upsbf.hip, K3u); even rates 2 / 8 / 10 / 12, c_in % 64 == 0, at most 64 folded noise rows

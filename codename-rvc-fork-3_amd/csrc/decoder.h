@@ -47,7 +47,7 @@ struct ConvW {
     DevBuf16 wu16;                // ... as bf16 pairs when the handle stores bf16 (two uint16 per word)
     DevBuf16 wx;                  // square 7 / 11-tap layers at >= 64 channels (fp32 storage): transformed taps split in three bf16 (winobf.hip)
     DevBuf16 wd;                  // bf16 storage, 128 / 256 channels where the fused pair does not apply: one-term direct-form fragments (convbf1.hip)
-    DevBuf16 wh;                  // arithmetic mode 1, square 128 / 256 channels where K3h is the faster kernel: fp16 (hi, lo 2^11) fragments (convh2.hip)
+    DevBuf16 wh;                  // arithmetic mode 1, square 128 / 256 channels where K3h is the faster kernel: fp16 (hi, lo 2^11) fragments (convbf1.hip)
     int c_in = 0, c_out = 0, k = 0;
 };
 

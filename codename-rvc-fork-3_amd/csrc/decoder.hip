@@ -455,9 +455,9 @@ int build_conv(const rvc_decoder *d, const std::string &prefix, int c_out, int c
             std::vector<uint16_t> halves(words.size() * 2);
             memcpy(halves.data(), words.data(), words.size() * 4);
             if (out->wu16.upload(halves)) return 1;
-            if (convbf1_supported(c_out, k, 1) && convbf1_preferred(c_out, k)) {   // direct form with one-term taps (K3d): taken before the Winograd form
+            if (convbf1_supported(c_out, k, 1) && convbf1_preferred(CB1_BF16W, c_out, k)) {   // direct form with one-term taps (K3d): taken before the Winograd form
                 std::vector<uint16_t> frags;
-                convbf1_pack_host(w->data.data(), c_out, k, &frags);
+                convbf1_pack_host(CB1_BF16W, w->data.data(), c_out, k, &frags);
                 if (out->wd.upload(frags)) return 1;
             }
             if (winobf_enabled() && winobf_supported(c_in, c_out, k, 1)) {   // the bf16-matrix-core form on the bf16-VALUED taps: a transformed
@@ -475,9 +475,9 @@ int build_conv(const rvc_decoder *d, const std::string &prefix, int c_out, int c
             if (out->wu.upload(packed)) return 1;
             // arithmetic mode 1: the fp16-pair fragments (K3h), taken before every other form; a tap tensor the pair cannot hold
             // (non-finite, |w| > 65504) keeps its layer on the exact path
-            if (d->arithmetic == 1 && convh2_supported(c_out, k, 1) && convh2_preferred(c_out, k)) {
+            if (d->arithmetic == 1 && convbf1_supported(c_out, k, 1) && convbf1_preferred(CB1_F16X2, c_out, k)) {
                 std::vector<uint16_t> frags;
-                if (!convh2_pack_host(w->data.data(), c_out, k, &frags) && out->wh.upload(frags)) return 1;
+                if (!convbf1_pack_host(CB1_F16X2, w->data.data(), c_out, k, &frags) && out->wh.upload(frags)) return 1;
             }
             if (winobf_enabled() && winobf_supported(c_in, c_out, k, 1)) {   // third copy: the bf16-matrix-core form's fragments
                 std::vector<uint16_t> frags;

@@ -4,7 +4,7 @@
 // and a product is  w x ~= w_hi x_hi + 2^-11 (w_hi x_lo + w_lo x_hi);  the dropped w_lo x_lo is <= 2^-22 |w x|.
 // The 2^11 keeps lo a NORMAL fp16 wherever hi is one (|v - hi| <= 2^-11 |hi| would otherwise sit 11 binades nearer the subnormals).
 // Range: |v| <= 65504 (above it hi is inf).  Below |v| ~ 2^-14 hi is an fp16 subnormal: the pair then still holds v to
-// 2^-25 / 2^11 absolute, as long as subnormal operands are not flushed (convh2.hip says what the hardware does).
+// 2^-25 / 2^11 absolute, as long as subnormal operands are not flushed (convbf1.hip says what the hardware does).
 #pragma once
 
 #include <hip/hip_runtime.h>

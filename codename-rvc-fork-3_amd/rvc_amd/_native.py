@@ -660,61 +660,53 @@ def resblock_bf16x3_forward(x, u_packed, b1, b2, k, dilation=1, slope=0.1, acc=N
     return y
 
 
-# ---- K3d: one square conv with bf16-valued taps, direct form (C = 128 / 256) --------------------------------------
-def conv1d_bf16w_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    """nn.Conv1d weight [c, c, k] -> one-term direct-form fragment slab on the device (the taps ROUNDED to bf16)."""
+# ---- K3d / K3h: one square conv in direct form (C = 128 / 256), one kernel template (csrc/convbf1.hip) on two operand formats ---
+def _conv1d_direct_pack(stem: str, label: str, w: torch.Tensor, device) -> torch.Tensor:
+    """`stem`: the entry points' common prefix (rvc_conv1d_bf16w / rvc_conv1d_f16x2), `label`: what messages call the format."""
     w = w.detach().float().cpu().contiguous()
     c, c_in, k = w.shape
     if c != c_in:
-        raise NativeError(f"conv1d_bf16w: a square conv expected, got {tuple(w.shape)}")
+        raise NativeError(f"{label}: a square conv expected, got {tuple(w.shape)}")
     n = c_size_t()
-    _check(_lib.rvc_conv1d_bf16w_weight_bytes(c, k, ctypes.byref(n)), "rvc_conv1d_bf16w_weight_bytes")
+    _check(getattr(_lib, stem + "_weight_bytes")(c, k, ctypes.byref(n)), stem + "_weight_bytes")
     u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_conv1d_bf16w_pack_weight(w.data_ptr(), c, k, u.data_ptr(), _stream()), "rvc_conv1d_bf16w_pack_weight")
+    _check(getattr(_lib, stem + "_pack_weight")(w.data_ptr(), c, k, u.data_ptr(), _stream()), stem + "_pack_weight")
     return u
+
+
+def _conv1d_direct_forward(stem: str, label: str, x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out):
+    x = _dev_f32(x, "x")
+    b, c, length = x.shape
+    y = out if out is not None else torch.empty_like(x)
+    if y.data_ptr() == x.data_ptr():
+        raise NativeError(f"{label}: x and y must not alias")
+    _check(getattr(_lib, stem + "_forward")(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                            res.data_ptr() if res is not None else None, acc.data_ptr() if acc is not None else None,
+                                            y.data_ptr(), b, c, length, k, dilation, float(slope_in), float(out_scale), _stream()),
+           stem + "_forward")
+    return y
+
+
+def conv1d_bf16w_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
+    """nn.Conv1d weight [c, c, k] -> one-term direct-form fragment slab on the device (the taps ROUNDED to bf16)."""
+    return _conv1d_direct_pack("rvc_conv1d_bf16w", "conv1d_bf16w", w, device)
 
 
 def conv1d_bf16w_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
     """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3d)."""
-    x = _dev_f32(x, "x")
-    b, c, length = x.shape
-    y = out if out is not None else torch.empty_like(x)
-    if y.data_ptr() == x.data_ptr():
-        raise NativeError("conv1d_bf16w: x and y must not alias")
-    _check(_lib.rvc_conv1d_bf16w_forward(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         res.data_ptr() if res is not None else None, acc.data_ptr() if acc is not None else None,
-                                         y.data_ptr(), b, c, length, k, dilation, float(slope_in), float(out_scale), _stream()),
-           "rvc_conv1d_bf16w_forward")
-    return y
+    return _conv1d_direct_forward("rvc_conv1d_bf16w", "conv1d_bf16w", x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out)
 
 
-# ---- K3h: one square conv with fp32 taps on error-corrected fp16 pairs, direct form (C = 128 / 256) ---------------
 def conv1d_f16x2_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
     """nn.Conv1d weight [c, c, k] -> fp16 (hi, lo * 2^11) direct-form fragment slab on the device; raises for a tap that is
     non-finite or beyond +-65504."""
-    w = w.detach().float().cpu().contiguous()
-    c, c_in, k = w.shape
-    if c != c_in:
-        raise NativeError(f"conv1d_f16x2: a square conv expected, got {tuple(w.shape)}")
-    n = c_size_t()
-    _check(_lib.rvc_conv1d_f16x2_weight_bytes(c, k, ctypes.byref(n)), "rvc_conv1d_f16x2_weight_bytes")
-    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_conv1d_f16x2_pack_weight(w.data_ptr(), c, k, u.data_ptr(), _stream()), "rvc_conv1d_f16x2_pack_weight")
-    return u
+    return _conv1d_direct_pack("rvc_conv1d_f16x2", "conv1d_f16x2", w, device)
 
 
 def conv1d_f16x2_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3h)."""
-    x = _dev_f32(x, "x")
-    b, c, length = x.shape
-    y = out if out is not None else torch.empty_like(x)
-    if y.data_ptr() == x.data_ptr():
-        raise NativeError("conv1d_f16x2: x and y must not alias")
-    _check(_lib.rvc_conv1d_f16x2_forward(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         res.data_ptr() if res is not None else None, acc.data_ptr() if acc is not None else None,
-                                         y.data_ptr(), b, c, length, k, dilation, float(slope_in), float(out_scale), _stream()),
-           "rvc_conv1d_f16x2_forward")
-    return y
+    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3h: fp32 taps on
+    error-corrected fp16 pairs)."""
+    return _conv1d_direct_forward("rvc_conv1d_f16x2", "conv1d_f16x2", x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out)
 
 
 # ---- K3u: upsampling step (polyphase ConvTranspose1d + folded noise conv) on the bf16 matrix cores -----------------

@@ -450,7 +450,7 @@ int rvc_conv1d_bf16w_forward(const float *x_dev, const void *u_dev, const float 
  * the leaky ReLU (finite, less accurate results beyond; a NaN activation counts as -65504); pack_weight REFUSES taps with |w| > 65504
  * or a non-finite value.  Bit-reproducible from launch to launch.
  * u_dev: rvc_conv1d_f16x2_weight_bytes() = (C / 16) K (C / 32) 2048 bytes: per (64-channel chunk, tap, 16 input channels, 32 output
- * channels) one 1 KiB fragment of w_hi and one of w_lo 2^11.  Persistent 8-wave workgroups that own their CU (csrc/convh2.hip).
+ * channels) one 1 KiB fragment of w_hi and one of w_lo 2^11.  Persistent 8-wave workgroups that own their CU (csrc/convbf1.hip).
  * dilation 1..5, leaky slope in [0, 1], C * L * 4 < 2^31; y must not alias x (res and acc may alias y). */
 int rvc_conv1d_f16x2_weight_bytes(int c, int k, size_t *bytes);
 int rvc_conv1d_f16x2_pack_weight(const float *w_host, int c, int k, void *u_dev, void *stream);

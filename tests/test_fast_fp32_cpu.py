@@ -1,4 +1,4 @@
-"""The C ABI of the opt-in fast-fp32 vocoder mode (K3h, csrc/convh2.hip: fp32 taps and activations as error-corrected fp16 pairs) as far
+"""The C ABI of the opt-in fast-fp32 vocoder mode (K3h, csrc/convbf1.hip: fp32 taps and activations as error-corrected fp16 pairs) as far
 as it can be shown without a device: the size query accepts exactly the documented shapes and returns the documented byte count, the
 pack refuses taps an fp16 pair cannot hold BEFORE it touches the slab, and rvc_decoder_set_arithmetic refuses what its header comment
 says it refuses.  Every refusal names its entry point in rvc_last_error()."""

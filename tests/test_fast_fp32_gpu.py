@@ -1,4 +1,4 @@
-"""The opt-in fast-fp32 vocoder mode on the GPU: K3h (csrc/convh2.hip, rvc_conv1d_f16x2_*: one square ResBlock conv with fp32 taps and
+"""The opt-in fast-fp32 vocoder mode on the GPU: K3h (csrc/convbf1.hip, rvc_conv1d_f16x2_*: one square ResBlock conv with fp32 taps and
 activations as error-corrected fp16 pairs, three matrix products per multiply-add) at kernel level against float64 and against the
 exact bf16x3 Winograd form it replaces; the decoder handle with arithmetic="fp16x2" against the oracle and against the exact handle;
 VoiceConverter.dec_arithmetic end to end.  Gates are the project's own for these layers (6e-5 at |y| ~ 1, 1.5 x the exact path's relative

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""The opt-in fast-fp32 vocoder mode (K3h, convh2.hip: fp32 taps and activations as error-corrected fp16 pairs, three matrix products per
+"""The opt-in fast-fp32 vocoder mode (K3h, convbf1.hip: fp32 taps and activations as error-corrected fp16 pairs, three matrix products per
 multiply-add) against the exact path, at the cfg-2 vocoder's 256- and 128-channel stage lengths (30 s at 48 kHz: 38 376 and 383 760 samples).
 
 Per (C, K, dilation): the (dilated conv, conv + residual) pair of one ResBlock dilation as two launches of K3h against what the exact
 handle runs for that layer -- two launches of the bf16x3 Winograd form (K3y, winobf2.hip), or the fused pair (K3f, resblock_bf.hip) at
 C = 128 with 3 taps.  Both sides in one process, interleaved per shape, HIP events, median of 5 batches of 6 pairs.
 Then one 30 s NSF-48k decoder forward with arithmetic "exact" and "fp16x2" (median of 7 after 2 warm-ups), and their waveform difference.
-convh2_preferred (convh2.hip) takes the (C, K) where K3h wins here; profiles/fastfp32_conv_shapes.txt is this tool's output."""
+convbf1_preferred(CB1_F16X2, ..) (convbf1.hip) takes the (C, K) where K3h wins here; profiles/fastfp32_conv_shapes.txt is this tool's output."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "codename-rvc-fork-3_amd")]
