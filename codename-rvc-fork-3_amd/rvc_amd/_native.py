@@ -162,6 +162,12 @@ SYMBOLS = {
     "rvc_comm_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_char_p, c_size_t]),
     "rvc_index_broadcast": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "rvc_checksum64": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rvc_glu_dwconv_silu_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "rvc_layernorm_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p]),
+    "rvc_groupnorm_workspace_bytes": (c_int, [c_int, c_int64, c_int, POINTER(c_size_t)]),
+    "rvc_groupnorm_lrelu_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_int64, c_void_p,
+                                        c_size_t, c_void_p]),
+    "rvc_fcpe_decode_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -775,6 +781,57 @@ def linear_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, out_features: i
                                   res.data_ptr() if res is not None else None, y.data_ptr(), n_rows, in_features, out_features,
                                   {"none": 0, "gelu": 1}[act], _stream()), "rvc_linear_bf16x3")
     return y
+
+
+# ---- K15: FCPE between its GEMMs (csrc/fcpe.hip) -------------------------------------------------------------------------
+def glu_dwconv_silu(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """silu(depthwise_conv_K(x[:, :C] * sigmoid(x[:, C:]))) along the rows of x [n_rows, 2C]; w [C, K] (K odd, <= 31), bias [C]."""
+    x, w, bias = _dev_f32(x, "x"), _dev_f32(w, "w"), _dev_f32(bias, "bias")
+    n_rows, c = x.shape[0], x.shape[1] // 2
+    y = torch.empty((n_rows, c), dtype=torch.float32, device=x.device)
+    _check(_lib.rvc_glu_dwconv_silu_f32(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), n_rows, c, w.shape[1], _stream()),
+           "rvc_glu_dwconv_silu_f32")
+    return y
+
+
+def layernorm_rows(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+    """nn.LayerNorm over the last axis of x [..., F] (F a multiple of 64, <= 1024)."""
+    x = _dev_f32(x, "x")
+    f = x.shape[-1]
+    y = torch.empty_like(x)
+    _check(_lib.rvc_layernorm_rows_f32(x.data_ptr(), _dev_f32(gamma, "gamma").data_ptr(), _dev_f32(beta, "beta").data_ptr(), float(eps),
+                                       y.data_ptr(), x.numel() // f, f, _stream()), "rvc_layernorm_rows_f32")
+    return y
+
+
+def groupnorm_lrelu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float = 1e-5,
+                    slope: float = 0.01) -> torch.Tensor:
+    """leaky_relu(nn.GroupNorm(groups, C)(x), slope) for channel-major x [C, L]."""
+    x = _dev_f32(x, "x")
+    c, length = x.shape
+    need = c_size_t()
+    _check(_lib.rvc_groupnorm_workspace_bytes(c, length, groups, ctypes.byref(need)), "rvc_groupnorm_workspace_bytes")
+    ws = _ws.get("groupnorm", need.value, x.device)
+    y = torch.empty_like(x)
+    _check(_lib.rvc_groupnorm_lrelu_f32(x.data_ptr(), _dev_f32(gamma, "gamma").data_ptr(), _dev_f32(beta, "beta").data_ptr(), groups,
+                                        float(eps), float(slope), y.data_ptr(), c, length, ws.data_ptr(), ws.numel(), _stream()),
+           "rvc_groupnorm_lrelu_f32")
+    return y
+
+
+def fcpe_decode(logits: torch.Tensor, cent_table: torch.Tensor, out_dims: int, threshold: float, f0_min: float,
+                want_latent: bool = False):
+    """logits [n_rows, ld >= out_dims] -> (f0 [n_rows] fp32 in Hz, 0 = unvoiced; latent [n_rows, out_dims] or None)."""
+    logits, cent_table = _dev_f32(logits, "logits"), _dev_f32(cent_table, "cent_table")
+    n_rows, ld = logits.shape
+    if cent_table.numel() != out_dims:
+        raise NativeError(f"cent_table has {cent_table.numel()} entries, out_dims is {out_dims}")
+    f0 = torch.empty(n_rows, dtype=torch.float32, device=logits.device)
+    latent = torch.empty((n_rows, out_dims), dtype=torch.float32, device=logits.device) if want_latent else None
+    _check(_lib.rvc_fcpe_decode_f32(logits.data_ptr(), cent_table.data_ptr(), out_dims, ld, float(threshold), float(f0_min),
+                                    f0.data_ptr(), latent.data_ptr() if latent is not None else None, n_rows, _stream()),
+           "rvc_fcpe_decode_f32")
+    return f0, latent
 
 
 # ---- K12: HuBERT's transformer GEMMs with both operands pre-split (csrc/linbf.hip) ---------------------------------------

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from scipy import signal
 
 from rvc_amd import _native
+from rvc_amd.lib.predictors.FCPE import FCPE
 from rvc_amd.lib.predictors.RMVPE import RMVPE0Predictor
 
 FILTER_ORDER = 5
@@ -207,6 +208,7 @@ class Pipeline:
         self.device = config.device
         rmvpe_path = os.path.join("rvc", "models", "predictors", "rmvpe.pt")  # pipeline.py:207-210
         self.model_rmvpe = RMVPE0Predictor(rmvpe_path if os.path.isfile(rmvpe_path) else None, device=self.device)
+        self.model_fcpe = None     # built at the first f0_method="fcpe" call (or by load_fcpe_state_dict), then kept
         # shared by the host threads of VoiceConverter.convert_batch: filled under the lock, read-only afterwards
         self._lock = threading.Lock()
         self._index_cache = {}
@@ -222,6 +224,18 @@ class Pipeline:
     # ---- additions -------------------------------------------------------------------------------------
     def load_rmvpe_state_dict(self, sd):
         self.model_rmvpe.load_state_dict(sd)
+
+    def load_fcpe_state_dict(self, ckpt):
+        """Install an FCPE checkpoint ({"config_dict": ..., "model": state_dict}) for f0_method="fcpe"."""
+        self.model_fcpe = FCPE(self.window, int(self.f0_min), int(self.f0_max), self.sample_rate, self.device, checkpoint=ckpt)
+
+    def _fcpe(self):
+        """The cached FCPE predictor (pipeline.py:359-371 reloads fcpe.pt on every call; the weights are packed once here)."""
+        with self._lock:
+            if self.model_fcpe is None:
+                self.model_fcpe = FCPE(self.window, int(self.f0_min), int(self.f0_max), self.sample_rate, self.device,
+                                       model_path=os.path.join("rvc", "models", "predictors", "fcpe.pt"))
+            return self.model_fcpe
 
     def set_index(self, big_npy):
         """Install a feature index directly (N x 768 float32) instead of reading a faiss file per call."""
@@ -249,9 +263,16 @@ class Pipeline:
     # ---- F0 ------------------------------------------------------------------------------------------------
     def get_f0(self, input_audio_path, x, p_len, pitch, f0_method, filter_radius, hop_length, f0_autotune,
                f0_autotune_strength, inp_f0=None):
-        """pipeline.py:322-410, rmvpe branch (the other estimators are out of scope)."""
+        """pipeline.py:322-410, the rmvpe and fcpe branches (crepe, crepe-tiny and hybrid[...] are out of scope).
+
+        For "fcpe" the reference hands ``filter_radius`` to the estimator as its CONFIDENCE THRESHOLD (pipeline.py:370), and so does
+        this: with ``convert_audio``'s default filter_radius = 3 no latent (a sigmoid) exceeds it, every frame is masked and the
+        contour is all zeros.  Pass a threshold such as 0.006 to use FCPE."""
+        if f0_method == "fcpe":
+            f0 = self._fcpe().compute_f0(x, p_len=p_len, filter_radius=filter_radius)
+            return self._postprocess_f0(f0, pitch, f0_autotune, inp_f0, f0_autotune_strength)
         if f0_method != "rmvpe":
-            raise NotImplementedError(f"f0_method={f0_method!r}: only 'rmvpe' is implemented")
+            raise NotImplementedError(f"f0_method={f0_method!r}: only 'rmvpe' and 'fcpe' are implemented")
         if torch.is_tensor(x):
             f0 = self.model_rmvpe.infer_from_audio_device(x, thred=0.03).cpu().numpy()
         else:
@@ -455,33 +476,43 @@ class Pipeline:
                 side = self._f0_streams.get(main.cuda_stream)
                 if side is None:
                     side = self._f0_streams[main.cuda_stream] = torch.cuda.Stream(device=self.device)
-            if f0_method != "rmvpe":
-                raise NotImplementedError(f"f0_method={f0_method!r}: only 'rmvpe' is implemented")
-            gi, n_f0 = self.model_rmvpe.front_half_device(audio_dev)
-            side.wait_stream(main)
-            gi.record_stream(side)
-            with torch.cuda.stream(side):
-                f0_dev = self.model_rmvpe.back_half_device(gi, n_f0, thred=0.03, taps=self.debug_taps)
-                if self.debug_taps is not None:
-                    self.debug_taps["f0_raw"] = f0_dev
-                if inp_f0 is None and f0_autotune is not True:
-                    # the contour never leaves HBM and the host never waits for it: everything below is enqueued
-                    # while the GPU is still busy with HuBERT
-                    pitch, pitchf = self._postprocess_f0_device(f0_dev, pitch)
-                    pitch = pitch[:p_len].unsqueeze(0)
-                    pitchf = pitchf[:p_len].unsqueeze(0).float()
-            feats_list = [self._extract_features(model, audio_dev[a], index, big_npy, index_rate, version) for a, _ in plan]
-            if inp_f0 is None and f0_autotune is not True:
-                main.wait_stream(side)
-                pitch.record_stream(main)
-                pitchf.record_stream(main)
-            else:  # f0-file override: the reference's host code, on the host
-                with torch.cuda.stream(side):
-                    f0_host = f0_dev.cpu().numpy()  # waits for the side stream only
-                pitch, pitchf = self._postprocess_f0(f0_host, pitch, f0_autotune, inp_f0, f0_autotune_strength)
+            if f0_method not in ("rmvpe", "fcpe"):
+                raise NotImplementedError(f"f0_method={f0_method!r}: only 'rmvpe' and 'fcpe' are implemented")
+            if f0_method == "fcpe":
+                # FCPE's contour ends in the reference's host code (resize + gap interpolation, fcpe.py:30-77), so it takes the
+                # host route the f0-file branch takes: the network on the main stream, one device -> host read, float64 on the host
+                pitch, pitchf = self.get_f0("input_audio_path", audio_dev, p_len, pitch, f0_method, filter_radius, hop_length,
+                                            f0_autotune, f0_autotune_strength, inp_f0)
                 pitch, pitchf = pitch[:p_len], pitchf[:p_len]
                 pitch = torch.tensor(pitch, device=self.device).unsqueeze(0).long()
                 pitchf = torch.tensor(pitchf, device=self.device).unsqueeze(0).float()
+                feats_list = [self._extract_features(model, audio_dev[a], index, big_npy, index_rate, version) for a, _ in plan]
+            else:
+                gi, n_f0 = self.model_rmvpe.front_half_device(audio_dev)
+                side.wait_stream(main)
+                gi.record_stream(side)
+                with torch.cuda.stream(side):
+                    f0_dev = self.model_rmvpe.back_half_device(gi, n_f0, thred=0.03, taps=self.debug_taps)
+                    if self.debug_taps is not None:
+                        self.debug_taps["f0_raw"] = f0_dev
+                    if inp_f0 is None and f0_autotune is not True:
+                        # the contour never leaves HBM and the host never waits for it: everything below is enqueued
+                        # while the GPU is still busy with HuBERT
+                        pitch, pitchf = self._postprocess_f0_device(f0_dev, pitch)
+                        pitch = pitch[:p_len].unsqueeze(0)
+                        pitchf = pitchf[:p_len].unsqueeze(0).float()
+                feats_list = [self._extract_features(model, audio_dev[a], index, big_npy, index_rate, version) for a, _ in plan]
+                if inp_f0 is None and f0_autotune is not True:
+                    main.wait_stream(side)
+                    pitch.record_stream(main)
+                    pitchf.record_stream(main)
+                else:  # f0-file override: the reference's host code, on the host
+                    with torch.cuda.stream(side):
+                        f0_host = f0_dev.cpu().numpy()  # waits for the side stream only
+                    pitch, pitchf = self._postprocess_f0(f0_host, pitch, f0_autotune, inp_f0, f0_autotune_strength)
+                    pitch, pitchf = pitch[:p_len], pitchf[:p_len]
+                    pitch = torch.tensor(pitch, device=self.device).unsqueeze(0).long()
+                    pitchf = torch.tensor(pitchf, device=self.device).unsqueeze(0).float()
             for (feats, feats0, n_audio), (_, ps) in zip(feats_list, plan):
                 if noise_seed is not None:
                     for _ in range(12):  # transformers' HuBERT LayerDrop draws, made per segment before the synthesizer's

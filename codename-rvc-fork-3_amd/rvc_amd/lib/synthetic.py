@@ -442,6 +442,17 @@ def synth_audio(n_samples: int, seed: int = 0, sr: int = 16000) -> np.ndarray:
     return 0.3 * env * np.sin(phase) + 0.01 * rng.standard_normal(n_samples)
 
 
+def synth_gated_glide(n_samples: int, seed: int = 0, sr: int = 16000) -> np.ndarray:
+    """16 kHz mono float64 two-harmonic glide (140 -> 260 Hz with vibrato), gated on and off at least once, + 0.03 N(0,1): voiced
+    stretches and noise-only ones, which an estimator with a confidence mask (FCPE) must tell apart."""
+    rng = np.random.default_rng([seed, 15])
+    t = np.arange(n_samples, dtype=np.float64) / sr
+    f = 140.0 + 120.0 * t / max(t[-1], 1e-9) + 15.0 * np.sin(2 * np.pi * 3.0 * t)
+    ph = 2 * np.pi * np.cumsum(f) / sr
+    gate = 0.5 * (1 + np.tanh(8 * np.sin(2 * np.pi * t * max(1.3, 1.5 * sr / n_samples))))
+    return 0.3 * gate * (np.sin(ph) + 0.5 * np.sin(2 * ph)) + 0.03 * rng.standard_normal(n_samples)
+
+
 def synth_index(n_rows: int, dim: int = 768, seed: int = 0, *, n_centres: int = 512,
                 jitter: float = 0.05, centres: np.ndarray | None = None) -> np.ndarray:
     """Clustered ``N x 768`` float32 feature index (HuBERT-like rows + jitter).
@@ -460,3 +471,41 @@ def synth_index(n_rows: int, dim: int = 768, seed: int = 0, *, n_centres: int = 
         which = rng.integers(0, centres.shape[0], size=e - s)
         out[s:e] = centres[which] + rng.standard_normal((e - s, dim), dtype=np.float32) * np.float32(jitter)
     return out
+
+
+# ---- FCPE (rvc/lib/predictors/torchfcpe) -----------------------------------------------------
+
+def make_fcpe_checkpoint(seed: int = 0, *, hidden: int = 512, layers: int = 6) -> dict:
+    """A synthetic ``fcpe.pt`` in the reference's layout ``{"config_dict": ..., "model": state_dict}`` (models_infer.py:353-364) with
+    the bundled model's configuration: conv-only conformer, 128-band mel at 16 kHz, 360 pitch classes.  The state dict carries the
+    names ``CFNaiveMelPE(...).state_dict()`` has (weight norm of ``output_proj`` in the ``parametrizations`` spelling).  The output
+    projection's rows have norm ~0.5, so the logits spread by about that much and the latents stay clear of the sigmoid's
+    saturation, where the gap between the two largest of a frame collapses."""
+    out_dims, n_mels, f0_min, f0_max = 360, 128, 32.70, 1975.5
+    g = _Gen(seed)
+    g.conv("input_stack.0", hidden, n_mels, 3)
+    g.layer_norm("input_stack.1", hidden)
+    g.conv("input_stack.3", hidden, hidden, 3)
+    for i in range(layers):
+        p = f"net.encoder_layers.{i}"
+        g.layer_norm(p + ".conformer.net.0", hidden)
+        g.conv(p + ".conformer.net.2", 4 * hidden, hidden, 1, gain=1.0)
+        g.conv(p + ".conformer.net.4.conv", 2 * hidden, 1, 31, gain=1.0)
+        g.conv(p + ".conformer.net.6", hidden, 2 * hidden, 1, gain=1.0)
+        g.layer_norm(p + ".norm", hidden)            # the attention branch's norm: present in the module, unused when conv_only
+    g.layer_norm("norm", hidden)
+    g.normal("output_proj.bias", (out_dims,), 0.05)
+    g.normal("output_proj.parametrizations.weight.original1", (out_dims, hidden), 1.0 / math.sqrt(hidden))
+    jitter = 1.0 + 0.1 * g._rng("output_proj.g").standard_normal((out_dims, 1), dtype=np.float32)
+    g.out["output_proj.parametrizations.weight.original0"] = torch.from_numpy((0.5 * jitter).astype(np.float32))
+    lo, hi = (1200.0 * torch.log2(torch.tensor([f], dtype=torch.float32) / 10.0)[0] for f in (f0_min, f0_max))   # models.py:95-100
+    g.out["cent_table"] = torch.linspace(lo, hi, out_dims)
+    g.out["gaussian_blurred_cent_mask"] = hi.clone()
+    config = {
+        "model": {"type": "CFNaiveMelPE", "hidden_dims": hidden, "n_layers": layers, "n_heads": 8, "out_dims": out_dims,
+                  "f0_min": f0_min, "f0_max": f0_max, "use_fa_norm": True, "conv_only": True, "conv_dropout": 0.1,
+                  "atten_dropout": 0.1, "use_harmonic_emb": False},
+        "mel": {"sr": 16000, "num_mels": n_mels, "n_fft": 1024, "win_size": 1024, "hop_size": 160, "fmin": 0, "fmax": 8000,
+                "clip_val": 1e-5},
+    }
+    return {"config_dict": config, "model": g.out}

@@ -1,10 +1,10 @@
 """Feature extraction for training data on the MI355X with the reference's surface (rvc/train/extract/extract.py:29-212):
-``FeatureInput`` (RMVPE f0 + coarse bins per utterance) and ``process_file_embedding`` (HuBERT features per utterance),
+``FeatureInput`` (RMVPE or FCPE f0 + coarse bins per utterance) and ``process_file_embedding`` (HuBERT features per utterance),
 fanned out over the GPUs of the node exactly like the reference does -- one worker per device, files strided
 ``files[i::len(devices)]`` (extract.py:141-152, 196-208).  The networks and kernels are the inference path's own
-(rvc_amd.lib.predictors.RMVPE, rvc_amd.lib.hubert, librvc_amd K4/K5/K7): SURVEY §8f rank 4.
+(rvc_amd.lib.predictors.RMVPE / FCPE, rvc_amd.lib.hubert, librvc_amd K4/K5/K7/K15): SURVEY §8f rank 4.
 
-Out of scope, as for inference: crepe / fcpe estimators, audio decoding other than WAV (rvc_amd.lib.audio).
+Out of scope, as for inference: the crepe estimators, audio decoding other than WAV (rvc_amd.lib.audio).
 """
 from __future__ import annotations
 
@@ -31,9 +31,11 @@ class FeatureInput:
         self.model_rmvpe = None
 
     def compute_f0(self, audio_array, method, hop_length):
-        if method != "rmvpe":
-            raise NotImplementedError(f"f0 method {method!r}: only 'rmvpe' is built (SURVEY §2 item 10)")
-        return self.model_rmvpe.infer_from_audio(audio_array, thred=0.03)
+        if method == "rmvpe":
+            return self.model_rmvpe.infer_from_audio(audio_array, thred=0.03)
+        if method == "fcpe":                                  # extract.py:48-49
+            return self.model_fcpe.compute_f0(audio_array)
+        raise NotImplementedError(f"f0 method {method!r}: only 'rmvpe' and 'fcpe' are built (SURVEY §2 item 10)")
 
     def coarse_f0(self, f0):
         """extract.py:76-87"""
@@ -54,6 +56,16 @@ class FeatureInput:
         except Exception as error:
             print(f"An error occurred extracting file {inp_path} on {self.device}: {error}")
 
+    def load_fcpe(self, checkpoint=None):
+        """extract.py:112-122: the FCPE predictor of this worker's device, built once (fcpe.pt of the working directory, or the
+        given {"config_dict": ..., "model": state_dict})."""
+        from rvc_amd.lib.predictors.FCPE import FCPE
+        if checkpoint is not None or not hasattr(self, "model_fcpe"):
+            self.model_fcpe = FCPE(hop_length=self.hop, f0_min=int(self.f0_min), f0_max=int(self.f0_max), sampling_rate=self.fs,
+                                   device=self.device, model_path=os.path.join("rvc", "models", "predictors", "fcpe.pt"),
+                                   checkpoint=checkpoint)
+        return self.model_fcpe
+
     def process_files(self, files, f0_method, hop_length, device, threads=1, rmvpe_state_dict=None):
         """One device's share.  The reference runs `threads` host threads per device (extract.py:124-131); the GPU path is
         a stream of kernels per file, so files are simply walked in order on this device's stream."""
@@ -62,6 +74,8 @@ class FeatureInput:
         if f0_method == "rmvpe":
             path = os.path.join("rvc", "models", "predictors", "rmvpe.pt")
             self.model_rmvpe = RMVPE0Predictor(path if rmvpe_state_dict is None else None, device=device, state_dict=rmvpe_state_dict)
+        elif f0_method == "fcpe":
+            self.load_fcpe()
         with torch.cuda.device(device):
             for f in files:
                 self.process_file(f, f0_method, hop_length)

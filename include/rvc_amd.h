@@ -565,6 +565,35 @@ int rvc_posconv_bf16x3_pack_weight(const float *w_host, int d, int groups, int t
 int rvc_posconv_gelu_bf16x3(const float *x_dev, const void *a_dev, const float *bias_dev, float *y_dev, int64_t n_frames, int d,
                             int groups, int taps, int padding, void *stream);
 
+/* ---- K15: the FCPE pitch estimator between its GEMMs (csrc/fcpe.hip) ------------------------------------------------------------ *
+ * The conv-only conformer of rvc/lib/predictors/torchfcpe (f0_method = "fcpe"): its dense layers run on K11, these four fp32
+ * kernels are the rest.  Every entry checks its arguments before any device call and launches on `stream`.
+ * rvc_glu_dwconv_silu_f32: nn.GLU(dim=1) -> DepthWiseConv1d(K, same padding) -> nn.SiLU of ConformerConvModule
+ *   (model_conformer_naive.py:144-151) on time-major rows.  x_dev [n_rows][2C]: columns [0, C) the value, [C, 2C) the gate;
+ *   u[t][c] = x[t][c] * sigmoid(x[t][C + c]);  v[t][c] = bias[c] + sum_j w[c][j] * u[t + j - K/2][c], u = 0 outside [0, n_rows);
+ *   y_dev[t][c] = v * sigmoid(v).  w_dev [C][K], bias_dev [C], y_dev [n_rows][C].  C a multiple of 64, K odd, 1 <= K <= 31,
+ *   n_rows >= 1, every pointer 16-byte aligned.
+ * rvc_layernorm_rows_f32: nn.LayerNorm(F) per row of x_dev [n_rows][F] (model_conformer_naive.py:142, models.py:83): biased
+ *   variance from centred squares around the row mean (two passes, float64), gamma_dev / beta_dev [F].  F a multiple of 64, <= 1024.
+ * rvc_groupnorm_lrelu_f32: nn.GroupNorm(groups, C) -> nn.LeakyReLU(slope) of input_stack (models.py:66-71) on channel-major
+ *   x_dev / y_dev [C][L]; biased variance over the (C / groups) x L elements of a group, taken as per-workgroup centred partial sums
+ *   merged in float64.  workspace_dev: rvc_groupnorm_workspace_bytes(C, L, groups) bytes, 8-byte aligned.  groups divides C.
+ * rvc_fcpe_decode_f32: sigmoid + latent2cents_local_decoder + cent_to_f0 + the uv mask (models.py:120, 149-176, 246-251,
+ *   models_infer.py:204-207).  logits_dev [n_rows][ld], ld >= out_dims the row stride (columns >= out_dims are never read);
+ *   latent = sigmoid(logit); per row the maximum and the LOWEST index attaining it; the nine indices argmax - 4 .. argmax + 4, each
+ *   clamped to [0, out_dims - 1] (a clamped duplicate counts as often as it occurs); cents = sum(cent_table * latent) / sum(latent)
+ *   over the nine; f0 = 0 when max <= threshold, else 10 * 2^(cents / 1200), and 0 when that is below f0_min.  f0_dev [n_rows];
+ *   latent_dev [n_rows][out_dims] or NULL. */
+int rvc_glu_dwconv_silu_f32(const float *x_dev, const float *w_dev, const float *bias_dev, float *y_dev, int64_t n_rows, int C, int K,
+                            void *stream);
+int rvc_layernorm_rows_f32(const float *x_dev, const float *gamma_dev, const float *beta_dev, float eps, float *y_dev, int64_t n_rows,
+                           int F, void *stream);
+int rvc_groupnorm_workspace_bytes(int C, int64_t L, int groups, size_t *bytes);
+int rvc_groupnorm_lrelu_f32(const float *x_dev, const float *gamma_dev, const float *beta_dev, int groups, float eps, float slope,
+                            float *y_dev, int C, int64_t L, void *workspace_dev, size_t workspace_bytes, void *stream);
+int rvc_fcpe_decode_f32(const float *logits_dev, const float *cent_table_dev, int out_dims, int ld, float threshold, float f0_min,
+                        float *f0_dev, float *latent_dev, int64_t n_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
