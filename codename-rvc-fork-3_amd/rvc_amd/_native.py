@@ -168,6 +168,10 @@ SYMBOLS = {
     "rvc_groupnorm_lrelu_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_int64, c_void_p,
                                         c_size_t, c_void_p]),
     "rvc_fcpe_decode_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rvc_kmeans_workspace_bytes": (c_int, [c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "rvc_kmeans_assign": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_kmeans_update": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -278,6 +282,48 @@ def knn_blend(index: torch.Tensor, feats: torch.Tensor, d2: torch.Tensor, ids: t
     _check(_lib.rvc_knn_blend(index.data_ptr(), index.shape[1], feats.data_ptr(), d2.data_ptr(), ids.data_ptr(),
                               feats.shape[0], d2.shape[1], float(index_rate), out.data_ptr(), _stream()),
            "rvc_knn_blend")
+    return out
+
+
+# ---- K16 -----------------------------------------------------------------------------------------
+def _kmeans_workspace(n_rows: int, n_centroids: int, dim: int, device) -> torch.Tensor:
+    need = c_size_t()
+    _check(_lib.rvc_kmeans_workspace_bytes(n_rows, n_centroids, dim, ctypes.byref(need)), "rvc_kmeans_workspace_bytes")
+    return _ws.get("kmeans", need.value, device)
+
+
+def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
+    """-> (ids int32 [n], d2 float32 [n]): the nearest centroid of every row of x and its squared distance (rvc_kmeans_assign)."""
+    x, centroids = _dev_f32(x, "x"), _dev_f32(centroids, "centroids")
+    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
+        raise NativeError(f"x {tuple(x.shape)} and centroids {tuple(centroids.shape)} must be [n, d] and [k, d]")
+    n, d = x.shape
+    ids = torch.empty(n, dtype=torch.int32, device=x.device)
+    d2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    if n == 0:
+        return ids, d2
+    ws = _kmeans_workspace(n, centroids.shape[0], d, x.device)
+    _check(_lib.rvc_kmeans_assign(x.data_ptr(), n, d, centroids.data_ptr(), centroids.shape[0], ids.data_ptr(), d2.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), _stream()), "rvc_kmeans_assign")
+    return ids, d2
+
+
+def kmeans_update(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, old: torch.Tensor) -> torch.Tensor:
+    """Centroid j <- the mean of rows order[offsets[j] : offsets[j + 1]] of x (float64 sums), or old[j] when it has no member
+    (rvc_kmeans_update).  order: int32 [n], offsets: int64 [k + 1]."""
+    x, old = _dev_f32(x, "x"), _dev_f32(old, "old")
+    n, d = x.shape
+    k = old.shape[0]
+    if (not order.is_cuda or order.dtype != torch.int32 or order.numel() != n or not offsets.is_cuda
+            or offsets.dtype != torch.int64 or offsets.numel() != k + 1 or old.shape[1] != d):
+        raise NativeError("order must be an int32 HBM tensor [n], offsets an int64 HBM tensor [k + 1], old [k, d]")
+    if n == 0:
+        return old.clone()
+    order, offsets = order.contiguous(), offsets.contiguous()
+    out = torch.empty_like(old)
+    ws = _kmeans_workspace(n, k, d, x.device)
+    _check(_lib.rvc_kmeans_update(x.data_ptr(), n, d, order.data_ptr(), offsets.data_ptr(), k, old.data_ptr(), out.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), _stream()), "rvc_kmeans_update")
     return out
 
 

@@ -594,6 +594,39 @@ int rvc_groupnorm_lrelu_f32(const float *x_dev, const float *gamma_dev, const fl
 int rvc_fcpe_decode_f32(const float *logits_dev, const float *cent_table_dev, int out_dims, int ld, float threshold, float f0_min,
                         float *f0_dev, float *latent_dev, int64_t n_rows, void *stream);
 
+/* ---- K16: k-means for the feature-index builder -------------------------------------------------- *
+ * Replaces the CPU clustering of rvc/train/process/extract_index.py:43-69: `MiniBatchKMeans(n_clusters=10000).fit(big_npy)`
+ * above 2e5 rows, and the coarse-quantiser training + `add` of `faiss.index_factory(768, f"IVF{n_ivf},Flat")`.  Both are Lloyd
+ * iterations over the [n_rows, dim] fp32 feature matrix; the two device steps of one iteration are exported here and the host
+ * bookkeeping (sort by assignment, empty-cluster re-seeding, the inverted lists) is rvc_amd/lib/kmeans.py.
+ * Common contract: dim a multiple of 32 in [32, 1024]; n_centroids >= 1; n_rows >= 0; both below 2^31; x, the centroid arrays
+ * and the workspace 16-byte aligned; every argument is checked before anything touches the device; n_rows == 0 returns 0 and
+ * launches nothing; all launches are asynchronous on `stream`; each call is a pure function of its inputs (no atomics, fixed
+ * merge orders), so two calls give identical bits.
+ *
+ * rvc_kmeans_workspace_bytes: the scratch both calls ask for at this shape (one buffer serves both; the larger of the two):
+ *   assign   n_centroids floats (||c||^2) + stripes x n_rows x 8 bytes, where stripes =
+ *            min(ceil(1024 / ceil(n_rows / 128)), ceil(n_centroids / 512)) centroid stripes -- one from 131 k rows on: 16 MB at
+ *            2 M rows, which is one call;
+ *   update   (n_rows / 256 + n_centroids + 1) partial sums of dim doubles.
+ * rvc_kmeans_assign: out_ids_dev[r] = the centroid nearest to row r, out_d2_dev[r] = its squared distance.
+ *   Selection is by the GEMM-form score ||c||^2 - 2 x.c, the dot product on the exact-fp32 matrix cores as ONE fmaf chain
+ *   over k = 0 .. dim - 1; equal scores go to the lower centroid id; the result does not depend on tiling or striping.
+ *   out_d2 is sum_k (x_k - c_k)^2 of the chosen centroid only, evaluated directly in fp32: 64 interleaved fmaf chains
+ *   (chain l takes the 4-float groups l, l + 64, ...), summed by the butterfly l ^ 32, 16, 8, 4, 2, 1.  Rows and centroids that
+ *   do not fill a 128-tile are masked inside the kernel.
+ * rvc_kmeans_update: the members of centroid j are rows order_dev[offsets_dev[j] .. offsets_dev[j + 1]) (order_dev: n_rows int32
+ *   row ids, offsets_dev: n_centroids + 1 int64, ascending, as torch.argsort(ids, stable=True) + a cumulative bincount give
+ *   them); out[j] = (float)(float64 sum over the members in list order / count), or old_centroids_dev[j] when it has none.
+ *   Entries of order_dev that are negative or >= n_rows are skipped and not counted; offsets are clamped to [0, n_rows].  Lists
+ *   longer than 256 members are summed in pieces of 256 whose partial sums are added in piece order.  out may alias old. */
+int rvc_kmeans_workspace_bytes(int64_t n_rows, int64_t n_centroids, int dim, size_t *bytes);
+int rvc_kmeans_assign(const float *x_dev, int64_t n_rows, int dim, const float *centroids_dev, int64_t n_centroids,
+                      int32_t *out_ids_dev, float *out_d2_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+int rvc_kmeans_update(const float *x_dev, int64_t n_rows, int dim, const int32_t *order_dev, const int64_t *offsets_dev,
+                      int64_t n_centroids, const float *old_centroids_dev, float *out_centroids_dev, void *workspace_dev,
+                      size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
