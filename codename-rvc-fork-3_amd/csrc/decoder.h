@@ -140,8 +140,9 @@ int launch_unfold_src(const float *har, int batch, int64_t L, int64_t S, int64_t
                       hipStream_t stream);
 int launch_cond_bias(const float *pre_b, const float *cond_w, const float *cond_b, const float *g, int batch, int gin, int c0,
                      float *out, hipStream_t stream);
+// out [batch][n_out] = samples [o_lo, o_lo + n_out) of the L (n_out < 0: everything from o_lo on)
 int launch_conv_post(const float *x, const float *w, float bias, int batch, int c_in, int64_t L, float slope, float *out,
-                     hipStream_t stream);
+                     hipStream_t stream, int64_t o_lo = 0, int64_t n_out = -1);
 
 // refine.hip
 int refine_finalize(rvc_decoder *d);

@@ -71,14 +71,16 @@ nsf_carry_kernel(const float *__restrict__ f0, int64_t T, float sr, float upp, f
     }
 }
 
-// hifigan.py:186-226 + hifigan_nsf.py:50-51 for harmonic_num = 0
+// hifigan.py:186-226 + hifigan_nsf.py:50-51 for harmonic_num = 0.  Frames [i0, i0 + Tw) of the T: f0, carry and the noise are read at
+// their absolute positions, har [batch][Tw * upp] starts at frame i0 (the whole signal: i0 = 0, Tw = T).
 __global__ void __launch_bounds__(256)
 nsf_source_kernel(const float *__restrict__ f0, const float *__restrict__ carry, const float *__restrict__ randn,
-                  int64_t T, int upp, float sr, float lin_w, float lin_b, float *__restrict__ har) {
-    const int64_t L = T * upp;
+                  int64_t T, int64_t i0, int64_t Tw, int upp, float sr, float lin_w, float lin_b, float *__restrict__ har) {
+    const int64_t L = T * upp, Lw = Tw * upp;
     const int64_t b = blockIdx.y;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= L) return;
+    const int64_t tw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tw >= Lw) return;
+    const int64_t t = tw + i0 * upp;
     const int64_t i = t / upp;
     const int j = (int)(t - i * upp);
     const float f = f0[b * T + i];
@@ -88,7 +90,7 @@ nsf_source_kernel(const float *__restrict__ f0, const float *__restrict__ carry,
     const float uv = f > 0.f ? 1.f : 0.f;
     const float amp = __fadd_rn(__fmul_rn(uv, 0.003f), __fmul_rn(1.f - uv, (float)(0.1 / 3)));
     const float v = __fadd_rn(__fmul_rn(sine, uv), __fmul_rn(amp, randn[b * L + t]));
-    har[b * L + t] = tanhf(__fadd_rn(__fmul_rn(v, lin_w), lin_b));
+    har[b * Lw + tw] = tanhf(__fadd_rn(__fmul_rn(v, lin_w), lin_b));
 }
 
 // ---- MRF / RefineGAN sine generator (hifigan_mrf.py:129-175, refinegan.py:220-260) -------------------
@@ -100,6 +102,7 @@ struct MrfSrcParams {
     const float *f0; const float *rand_ini; const float *randn; float *har;
     double *p1; double *p2; int *wraps; float *tot_unused;
     int64_t T; int upp; int dim; float sr;
+    int64_t i0, Tw;                      // har [batch][Tw * upp] holds frames [i0, i0 + Tw) (pass 4 only; the prefixes and wraps cover all T)
     float lin_w[MRF_MAX_DIM]; float lin_b;
 };
 
@@ -216,7 +219,7 @@ __global__ void __launch_bounds__(64) mrf_wraps_kernel(MrfSrcParams p) {
 // pass 4: one block per (frame, b): in-frame prefix of the wrap flags, sines, noise, Linear(dim -> 1), tanh
 __global__ void __launch_bounds__(256) mrf_source_kernel(MrfSrcParams p) {
     __shared__ int wave_tot[4];
-    const int64_t i = blockIdx.x;
+    const int64_t i = blockIdx.x + p.i0;
     const int b = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t L = p.T * p.upp;
@@ -276,7 +279,7 @@ __global__ void __launch_bounds__(256) mrf_source_kernel(MrfSrcParams p) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int j = it * 256 + threadIdx.x;
-        if (it < n_it && j < p.upp) p.har[(int64_t)b * L + i * p.upp + j] = tanhf(out_acc[it] + p.lin_b);
+        if (it < n_it && j < p.upp) p.har[((int64_t)b * p.Tw + (i - p.i0)) * p.upp + j] = tanhf(out_acc[it] + p.lin_b);
     }
 }
 
@@ -314,15 +317,18 @@ cond_bias_kernel(const float *__restrict__ pre_b, const float *__restrict__ cond
 // (8 outputs per lane -- lanes 32 bytes apart, four half-coalesced loads per channel -- measured 262 us against 125.)  Blocks that
 // touch either end of the signal, and lengths that are not a multiple of 4, take the scalar path.  The sums run channel by channel,
 // tap by tap, in both paths.
+// Only the outputs [o_lo, o_lo + n_out) of the L are computed: out is [batch][n_out] (the whole signal: o_lo = 0, n_out = L).
 constexpr int POST_OUT = 4;      // outputs per lane
 __global__ void __launch_bounds__(256)
-conv_post_kernel(const float *__restrict__ x, const float *__restrict__ w, float bias, int c_in, int64_t L, float slope,
-                 float *__restrict__ out) {
+conv_post_kernel(const float *__restrict__ x, const float *__restrict__ w, float bias, int c_in, int64_t L, int64_t o_lo, int64_t n_out,
+                 float slope, float *__restrict__ out) {
     const int64_t b = blockIdx.y;
-    const int64_t t0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * POST_OUT;
-    const int64_t blk0 = (int64_t)blockIdx.x * blockDim.x * POST_OUT;
+    const int64_t t0 = o_lo + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * POST_OUT;
+    const int64_t blk0 = o_lo + (int64_t)blockIdx.x * blockDim.x * POST_OUT;
+    const int64_t o_hi = o_lo + n_out;
     const float *xb = x + b * c_in * L;
-    const bool fast = (L & 3) == 0 && (c_in & 3) == 0 && blk0 >= 4 && blk0 + (int64_t)blockDim.x * POST_OUT + 4 <= L;   // block-uniform
+    const bool fast = (L & 3) == 0 && (c_in & 3) == 0 && ((o_lo | n_out) & 3) == 0 && blk0 >= 4 &&
+                      blk0 + (int64_t)blockDim.x * POST_OUT + 4 <= L && blk0 + (int64_t)blockDim.x * POST_OUT <= o_hi;   // block-uniform
     if (fast) {
         float acc[POST_OUT];
 #pragma unroll
@@ -352,12 +358,12 @@ conv_post_kernel(const float *__restrict__ x, const float *__restrict__ w, float
                 }
             }
         }
-        *reinterpret_cast<f32x4 *>(out + b * L + t0) = f32x4{tanhf(acc[0]), tanhf(acc[1]), tanhf(acc[2]), tanhf(acc[3])};
+        *reinterpret_cast<f32x4 *>(out + b * n_out + (t0 - o_lo)) = f32x4{tanhf(acc[0]), tanhf(acc[1]), tanhf(acc[2]), tanhf(acc[3])};
         return;
     }
     // edge blocks / odd lengths: the same sums from clamped, unconditional scalar loads (a load behind a per-element bounds check is
     // waited for on its own: 896 serial round trips per lane made these two blocks most of the launch's duration)
-    if (t0 >= L) return;
+    if (t0 >= o_hi) return;
     float acc[POST_OUT];
 #pragma unroll
     for (int o = 0; o < POST_OUT; ++o) acc[o] = bias;
@@ -380,7 +386,7 @@ conv_post_kernel(const float *__restrict__ x, const float *__restrict__ w, float
     }
 #pragma unroll
     for (int o = 0; o < POST_OUT; ++o)
-        if (t0 + o < L) out[b * L + t0 + o] = tanhf(acc[o]);
+        if (t0 + o < o_hi) out[b * n_out + (t0 - o_lo) + o] = tanhf(acc[o]);
 }
 
 int launch_unfold_src(const float *har, int batch, int64_t L, int64_t S, int64_t P, int k_valid, int k_rows, int64_t nq, float *V,
@@ -399,9 +405,10 @@ int launch_cond_bias(const float *pre_b, const float *cond_w, const float *cond_
 }
 
 int launch_conv_post(const float *x, const float *w, float bias, int batch, int c_in, int64_t L, float slope, float *out,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL(conv_post_kernel, dim3((unsigned)ceil_div(L, 256 * POST_OUT), batch), dim3(256), 0, stream, x, w, bias, c_in, L, slope,
-                       out);
+                     hipStream_t stream, int64_t o_lo, int64_t n_out) {
+    if (n_out < 0) n_out = L - o_lo;
+    hipLaunchKernelGGL(conv_post_kernel, dim3((unsigned)ceil_div(n_out, 256 * POST_OUT), batch), dim3(256), 0, stream, x, w, bias, c_in, L,
+                       o_lo, n_out, slope, out);
     RVC_LAUNCH_CHECK();
     return 0;
 }
@@ -733,14 +740,17 @@ int branch_lanes_wanted(const rvc_decoder *d) {
     const int most = nk - 1 < MAX_BRANCH_LANES ? nk - 1 : MAX_BRANCH_LANES;
     return want < 0 || want > most ? most : want;
 }
-Layout make_layout(const rvc_decoder *d, int batch, int64_t T) {
+// T: frames of f0 (the phase carry / prefix buffers); Tw <= T: frames the source samples and the conv stack run over (the whole call:
+// Tw = T).  Every piece grows with its length, so the T-frame layout holds any window of the same call.
+Layout make_layout(const rvc_decoder *d, int batch, int64_t T, int64_t Tw) {
     Layout l;
     Carve c;
-    const int64_t L = T * d->upp;
+    const int64_t L = Tw * d->upp;
     l.har = c.take((size_t)batch * L * 4);
     l.carry = c.take((size_t)batch * T * 4);
     l.biasp = c.take((size_t)batch * d->cfg.upsample_initial_channel * 4);
-    int64_t len = T, max_cl = (int64_t)d->cfg.upsample_initial_channel * T, max_v = 0;
+    // (a window call parks its [in_channels][Tw] slice of z in buf[1] until conv_pre has read it)
+    int64_t len = Tw, max_cl = (int64_t)std::max(d->cfg.upsample_initial_channel, d->cfg.in_channels) * Tw, max_v = 0;
     for (const Stage &s : d->stages) {
         const int64_t nq = len + 1;
         max_v = std::max<int64_t>(max_v, (int64_t)s.vk_rows * nq);
@@ -764,7 +774,7 @@ Layout make_layout(const rvc_decoder *d, int batch, int64_t T) {
 extern "C" int rvc_decoder_workspace_bytes(const rvc_decoder *dec, int batch, int64_t n_frames, size_t *bytes) {
     if (!dec || !bytes || batch <= 0 || n_frames <= 0) return fail("rvc_decoder_workspace_bytes: bad argument");
     if (!dec->finalized) return fail("rvc_decoder_workspace_bytes: decoder not finalized");
-    *bytes = dec->cfg.kind == RVC_DEC_REFINE ? refine_workspace_bytes(dec, batch, n_frames) : make_layout(dec, batch, n_frames).total;
+    *bytes = dec->cfg.kind == RVC_DEC_REFINE ? refine_workspace_bytes(dec, batch, n_frames) : make_layout(dec, batch, n_frames, n_frames).total;
     return 0;
 }
 
@@ -816,21 +826,51 @@ extern "C" int rvc_decoder_set_concurrency_hint(rvc_decoder *dec, int utterances
     return 0;
 }
 
-extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const float *f0_dev, const float *g_dev,
-                                   const rvc_decoder_noise *noise, int batch, int64_t T, float *out_dev,
-                                   void *workspace_dev, size_t workspace_bytes, void *stream_) {
-    if (!d || !z_dev || !f0_dev || !g_dev || !noise || !out_dev || !workspace_dev) return fail("rvc_decoder_forward: null pointer");
-    ConcurrencyScope scope(d->concurrency.load(std::memory_order_relaxed));
-    if (!d->finalized) return fail("rvc_decoder_forward: decoder not finalized");
-    if (batch <= 0 || T <= 0) return fail("rvc_decoder_forward: empty batch");
-    if (!noise->src_randn_dev) return fail("rvc_decoder_forward: src_randn_dev is required");
-    if (d->cfg.kind == RVC_DEC_REFINE)
-        return refine_forward(d, z_dev, f0_dev, g_dev, noise, batch, T, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
+namespace {
+// Input frames on each side that an output frame depends on through z or the source samples: the dependency interval of one frame's
+// samples [0, upp) walked back through conv_post, every stage (the worst ResBlock branch, the noise conv's taps on har, the transposed
+// conv) and conv_pre.  Every layer is a convolution at a whole multiple of the frame rate, so the interval of frame i is this one
+// shifted by i frames.  (The running phase is not local: the carry / prefix kernels always see every frame.)
+int window_margin(const rvc_decoder_config &c) {
+    auto fdiv = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };   // floor(a / b), b > 0
+    int64_t upp = 1;
+    for (int i = 0; i < c.n_ups; ++i) upp *= c.upsample_rates[i];
+    int64_t a = -3, b = upp - 1 + 3;                       // conv_post: 7 taps
+    int64_t ha = 0, hb = upp - 1;                          // har samples
+    int64_t stride = 1;                                    // output samples per sample of stage i's output
+    for (int i = c.n_ups - 1; i >= 0; --i) {
+        const int rate = c.upsample_rates[i], ks = c.upsample_kernel_sizes[i];
+        const int pad = rate % 2 == 0 ? (ks - rate) / 2 : rate / 2 + rate % 2;                  // hifigan_nsf.py:113-117
+        int64_t field = 0;                                 // the widest branch: sum over its layers of the dilated conv + the plain one
+        for (int m = 0; m < c.n_res_kernels; ++m) {
+            const int h = (c.res_kernel_sizes[m] - 1) / 2;
+            int64_t f = 0;
+            for (int j = 0; j < c.n_res_dilations; ++j) f += (int64_t)h * c.res_dilations[j] + h;
+            field = std::max(field, f);
+        }
+        a -= field; b += field;
+        const int64_t nc_k = stride == 1 ? 1 : stride * 2 - stride % 2, nc_pad = stride == 1 ? 0 : (nc_k - stride) / 2;   // hifigan_nsf.py:142-144
+        ha = std::min(ha, a * stride - nc_pad);
+        hb = std::max(hb, b * stride + nc_k - 1 - nc_pad);
+        // ConvTranspose1d: output t reads input q where t = q * rate + kk - pad, 0 <= kk < ks
+        a = -fdiv(-(a + pad - ks + 1), rate);
+        b = fdiv(b + pad, rate);
+        stride *= rate;
+    }
+    a -= 3; b += 3;                                        // conv_pre: 7 taps
+    return (int)std::max(std::max(-a, b), std::max(-fdiv(ha, upp), fdiv(hb, upp)));
+}
+
+// Both entries: the frames [ext_lo, ext_lo + Tw) of the T go through the source-sample kernels and the conv stack (the phase carry /
+// prefixes always over all T), and the samples [o_lo, o_lo + n_out) of those Tw * upp are written to out_dev [batch][n_out].
+// rvc_decoder_forward: ext_lo = 0, Tw = T, o_lo = 0, n_out = T * upp.
+int decoder_run(rvc_decoder *d, const float *z_dev, const float *f0_dev, const float *g_dev, const rvc_decoder_noise *noise, int batch,
+                int64_t T, int64_t ext_lo, int64_t Tw, int64_t o_lo, int64_t n_out, float *out_dev, void *workspace_dev,
+                size_t workspace_bytes, hipStream_t stream) {
     const rvc_decoder_config &c = d->cfg;
     const bool mrf = c.kind == RVC_DEC_MRF;
     if (mrf && !noise->src_rand_dev) return fail("rvc_decoder_forward: src_rand_dev is required for the MRF decoder");
-    hipStream_t stream = (hipStream_t)stream_;
-    const Layout lay = make_layout(d, batch, T);
+    const Layout lay = make_layout(d, batch, T, Tw);
     if (workspace_bytes < lay.total) return fail("rvc_decoder_forward: workspace too small (%zu < %zu)", workspace_bytes, lay.total);
     char *ws = (char *)workspace_dev;
     float *har = (float *)(ws + lay.har);
@@ -842,7 +882,7 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
     const int n_side = (lay.n_buf - 4) / 2;
     BranchLanes *lanes = nullptr;
     if (n_side > 0 && lanes_for(d, stream, n_side, &lanes)) return 1;
-    const int64_t L = T * d->upp;
+    const int64_t L = Tw * d->upp;   // samples the stack produces
     const float sr = (float)c.sample_rate;
 
     // ---- source module ----
@@ -850,7 +890,7 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
         hipLaunchKernelGGL(nsf_carry_kernel, dim3(batch), dim3(256), 0, stream, f0_dev, T, sr, (float)d->upp, carry);
         RVC_LAUNCH_CHECK();
         hipLaunchKernelGGL(nsf_source_kernel, dim3((unsigned)ceil_div(L, 256), batch), dim3(256), 0, stream, f0_dev, carry,
-                           noise->src_randn_dev, T, d->upp, sr, d->lin_w[0], d->lin_b, har);
+                           noise->src_randn_dev, T, ext_lo, Tw, d->upp, sr, d->lin_w[0], d->lin_b, har);
         RVC_LAUNCH_CHECK();
     } else {
         MrfSrcParams sp;
@@ -858,15 +898,16 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
         sp.p1 = (double *)(ws + lay.p1); sp.p2 = (double *)(ws + lay.p2); sp.wraps = (int *)(ws + lay.wraps);
         sp.tot_unused = nullptr;
         sp.T = T; sp.upp = d->upp; sp.dim = d->dim; sp.sr = sr;
+        sp.i0 = ext_lo; sp.Tw = Tw;
         for (int h = 0; h < MRF_MAX_DIM; ++h) sp.lin_w[h] = d->lin_w[h];
         sp.lin_b = d->lin_b;
         hipLaunchKernelGGL(mrf_prefix_kernel<1>, dim3(batch), dim3(256), 0, stream, sp);
         RVC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrf_wraps_kernel, dim3((unsigned)T, d->dim, batch), dim3(64), 0, stream, sp);
+        hipLaunchKernelGGL(mrf_wraps_kernel, dim3((unsigned)T, d->dim, batch), dim3(64), 0, stream, sp);   // all T: pass 3 sums every frame's count
         RVC_LAUNCH_CHECK();
         hipLaunchKernelGGL(mrf_prefix_kernel<3>, dim3(batch), dim3(256), 0, stream, sp);
         RVC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrf_source_kernel, dim3((unsigned)T, batch), dim3(256), 0, stream, sp);
+        hipLaunchKernelGGL(mrf_source_kernel, dim3((unsigned)Tw, batch), dim3(256), 0, stream, sp);
         RVC_LAUNCH_CHECK();
     }
     if (d->tap_stage == -1 && d->tap_dev)
@@ -878,17 +919,22 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
                        c.gin_channels, c0, biasp);
     RVC_LAUNCH_CHECK();
     float *cur = buf[0];   // stage input / running sum
+    if (Tw != T) {         // the window's columns of z as rows of length Tw (in buf[1]: stage 0 writes it only after conv_pre has read)
+        RVC_HIP(hipMemcpy2DAsync(buf[1], (size_t)Tw * 4, z_dev + ext_lo, (size_t)T * 4, (size_t)Tw * 4, (size_t)batch * c.in_channels,
+                                 hipMemcpyDeviceToDevice, stream));
+        z_dev = buf[1];
+    }
     {
         ConvParams p;
-        p.x1 = z_dev; p.c1 = c.in_channels; p.slope1 = 1.f; p.x1_bstride = (int64_t)c.in_channels * T; p.l_in = T;
+        p.x1 = z_dev; p.c1 = c.in_channels; p.slope1 = 1.f; p.x1_bstride = (int64_t)c.in_channels * Tw; p.l_in = Tw;
         p.w = d->pre.w.p; p.bias = biasp; p.bias_bstride = c0;
-        p.y = cur; p.y_bstride = (int64_t)c0 * T; p.m_total = c0; p.c_out = c0; p.n_cols = T; p.l_out = T;
+        p.y = cur; p.y_bstride = (int64_t)c0 * Tw; p.m_total = c0; p.c_out = c0; p.n_cols = Tw; p.l_out = Tw;
         p.kw = 7; p.dil = 1; p.padl = 3; p.batch = batch;
         if (launch_conv(p, stream)) return 1;
     }
 
     // ---- upsample stages ----
-    int64_t len = T;
+    int64_t len = Tw;
     const int nd = c.n_res_dilations, nk = c.n_res_kernels;
     for (int i = 0; i < c.n_ups; ++i) {
         Stage &s = d->stages[i];
@@ -1034,5 +1080,54 @@ extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const flo
             RVC_HIP(hipMemcpyAsync(d->tap_dev, cur, (size_t)batch * bs * 4, hipMemcpyDeviceToDevice, stream));
     }
     if (len != L) return fail("decoder: internal length mismatch (%lld vs %lld)", (long long)len, (long long)L);
-    return launch_conv_post(cur, d->post_w.p, d->post_b, batch, d->post_cin, L, 0.01f, out_dev, stream);
+    return launch_conv_post(cur, d->post_w.p, d->post_b, batch, d->post_cin, L, 0.01f, out_dev, stream, o_lo, n_out);
+}
+}  // namespace
+
+extern "C" int rvc_decoder_forward(rvc_decoder *d, const float *z_dev, const float *f0_dev, const float *g_dev,
+                                   const rvc_decoder_noise *noise, int batch, int64_t T, float *out_dev,
+                                   void *workspace_dev, size_t workspace_bytes, void *stream_) {
+    if (!d || !z_dev || !f0_dev || !g_dev || !noise || !out_dev || !workspace_dev) return fail("rvc_decoder_forward: null pointer");
+    ConcurrencyScope scope(d->concurrency.load(std::memory_order_relaxed));
+    if (!d->finalized) return fail("rvc_decoder_forward: decoder not finalized");
+    if (batch <= 0 || T <= 0) return fail("rvc_decoder_forward: empty batch");
+    if (!noise->src_randn_dev) return fail("rvc_decoder_forward: src_randn_dev is required");
+    if (d->cfg.kind == RVC_DEC_REFINE)
+        return refine_forward(d, z_dev, f0_dev, g_dev, noise, batch, T, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
+    return decoder_run(d, z_dev, f0_dev, g_dev, noise, batch, T, 0, T, 0, T * d->upp, out_dev, workspace_dev, workspace_bytes,
+                       (hipStream_t)stream_);
+}
+
+extern "C" int rvc_decoder_window_margin(const rvc_decoder_config *cfg, int *frames) {
+    if (!cfg || !frames) return fail("rvc_decoder_window_margin: null pointer");
+    if (cfg->kind != RVC_DEC_NSF && cfg->kind != RVC_DEC_MRF && cfg->kind != RVC_DEC_REFINE)
+        return fail("rvc_decoder_window_margin: unknown decoder kind %d", cfg->kind);
+    if (cfg->n_ups < 1 || cfg->n_ups > 8) return fail("rvc_decoder_window_margin: n_ups out of range");
+    if (cfg->n_res_kernels < 1 || cfg->n_res_kernels > 4 || cfg->n_res_dilations < 1 || cfg->n_res_dilations > 4)
+        return fail("rvc_decoder_window_margin: resblock configuration out of range");
+    for (int i = 0; i < cfg->n_ups; ++i)
+        if (cfg->upsample_rates[i] < 1 || cfg->upsample_kernel_sizes[i] < cfg->upsample_rates[i])
+            return fail("rvc_decoder_window_margin: upsample stage %d: rate %d, kernel %d", i, cfg->upsample_rates[i], cfg->upsample_kernel_sizes[i]);
+    // RefineGAN: interpolated source, a down path -- its field has not been worked out
+    *frames = cfg->kind == RVC_DEC_REFINE ? -1 : window_margin(*cfg);
+    return 0;
+}
+
+extern "C" int rvc_decoder_forward_window(rvc_decoder *d, const float *z_dev, const float *f0_dev, const float *g_dev,
+                                          const rvc_decoder_noise *noise, int batch, int64_t T, int64_t keep_lo, int64_t keep_hi,
+                                          float *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream_) {
+    if (!d || !z_dev || !f0_dev || !g_dev || !noise || !out_dev || !workspace_dev) return fail("rvc_decoder_forward_window: null pointer");
+    ConcurrencyScope scope(d->concurrency.load(std::memory_order_relaxed));
+    if (!d->finalized) return fail("rvc_decoder_forward_window: decoder not finalized");
+    if (batch <= 0 || T <= 0) return fail("rvc_decoder_forward_window: empty batch");
+    if (keep_lo < 0 || keep_lo >= keep_hi || keep_hi > T)
+        return fail("rvc_decoder_forward_window: frames [%lld, %lld) are not a window of [0, %lld)", (long long)keep_lo, (long long)keep_hi, (long long)T);
+    if (!noise->src_randn_dev) return fail("rvc_decoder_forward_window: src_randn_dev is required");
+    if (d->cfg.kind == RVC_DEC_REFINE)
+        return fail("rvc_decoder_forward_window: RefineGAN's receptive field is not covered; use rvc_decoder_forward");
+    if (d->tap_dev) return fail("rvc_decoder_forward_window: a debug tap is set (rvc_decoder_set_tap); use rvc_decoder_forward");
+    const int64_t m = window_margin(d->cfg);
+    const int64_t ext_lo = std::max<int64_t>(0, keep_lo - m), ext_hi = std::min<int64_t>(T, keep_hi + m);
+    return decoder_run(d, z_dev, f0_dev, g_dev, noise, batch, T, ext_lo, ext_hi - ext_lo, (keep_lo - ext_lo) * d->upp,
+                       (keep_hi - keep_lo) * d->upp, out_dev, workspace_dev, workspace_bytes, (hipStream_t)stream_);
 }

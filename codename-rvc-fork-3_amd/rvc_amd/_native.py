@@ -92,6 +92,9 @@ SYMBOLS = {
     "rvc_decoder_workspace_bytes": (c_int, [c_void_p, c_int, c_int64, POINTER(c_size_t)]),
     "rvc_decoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(DecoderNoise), c_int, c_int64,
                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_decoder_window_margin": (c_int, [POINTER(DecoderConfig), POINTER(c_int)]),
+    "rvc_decoder_forward_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(DecoderNoise), c_int, c_int64, c_int64,
+                                           c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rvc_decoder_set_tap": (c_int, [c_void_p, c_int, c_void_p]),
     "rvc_decoder_set_concurrency_hint": (c_int, [c_void_p, c_int]),
     "rvc_decoder_set_branch_parallel": (c_int, [c_void_p, c_int]),
@@ -1079,6 +1082,38 @@ DEC_KINDS = {"HiFi-GAN": 0, "MRF HiFi-GAN": 1, "RefineGAN": 2}
 DEC_ARITHMETIC = {"exact": 0, "fp16x2": 1}
 
 
+def _decoder_config(vocoder, sr, *, in_channels=192, upsample_initial_channel=512, gin_channels=256,
+                    upsample_rates=(12, 10, 2, 2), upsample_kernel_sizes=(24, 20, 4, 4), res_kernel_sizes=(3, 7, 11),
+                    res_dilations=(1, 3, 5), weight_storage: str = "f32") -> DecoderConfig:
+    cfg = DecoderConfig()
+    cfg.kind = DEC_KINDS[vocoder]
+    cfg.sample_rate = sr
+    cfg.in_channels = in_channels
+    cfg.upsample_initial_channel = upsample_initial_channel
+    cfg.gin_channels = gin_channels
+    cfg.n_ups = len(upsample_rates)
+    for i, (u, k) in enumerate(zip(upsample_rates, upsample_kernel_sizes)):
+        cfg.upsample_rates[i] = int(u)
+        cfg.upsample_kernel_sizes[i] = int(k)
+    cfg.n_res_kernels = len(res_kernel_sizes)
+    for i, k in enumerate(res_kernel_sizes):
+        cfg.res_kernel_sizes[i] = int(k)
+    cfg.weight_storage = {"f32": 0, "bf16": 1}[weight_storage]
+    cfg.n_res_dilations = len(res_dilations)
+    for i, d in enumerate(res_dilations):
+        cfg.res_dilations[i] = int(d)
+    return cfg
+
+
+def decoder_window_margin(vocoder: str, sr: int = 48000, **config) -> int:
+    """rvc_decoder_window_margin for a vocoder configuration (Decoder's keyword arguments): input frames on each side that an
+    output frame depends on; -1 for RefineGAN (not covered).  A host computation: needs no device."""
+    cfg = _decoder_config(vocoder, sr, **config)
+    frames = c_int()
+    _check(_lib.rvc_decoder_window_margin(ctypes.byref(cfg), ctypes.byref(frames)), "rvc_decoder_window_margin")
+    return frames.value
+
+
 class Decoder:
     """Handle on the library's vocoder: weights are repacked into HBM once, forward() launches the chain."""
 
@@ -1092,23 +1127,10 @@ class Decoder:
             raise NativeError("rvc_amd.Decoder needs a HIP device (no CPU fallback)")
         if arithmetic not in DEC_ARITHMETIC:
             raise NativeError(f"rvc_amd.Decoder: arithmetic must be one of {sorted(DEC_ARITHMETIC)}, got {arithmetic!r}")
-        cfg = DecoderConfig()
-        cfg.kind = DEC_KINDS[vocoder]
-        cfg.sample_rate = sr
-        cfg.in_channels = in_channels
-        cfg.upsample_initial_channel = upsample_initial_channel
-        cfg.gin_channels = gin_channels
-        cfg.n_ups = len(upsample_rates)
-        for i, (u, k) in enumerate(zip(upsample_rates, upsample_kernel_sizes)):
-            cfg.upsample_rates[i] = int(u)
-            cfg.upsample_kernel_sizes[i] = int(k)
-        cfg.n_res_kernels = len(res_kernel_sizes)
-        for i, k in enumerate(res_kernel_sizes):
-            cfg.res_kernel_sizes[i] = int(k)
-        cfg.weight_storage = {"f32": 0, "bf16": 1}[weight_storage]
-        cfg.n_res_dilations = len(res_dilations)
-        for i, d in enumerate(res_dilations):
-            cfg.res_dilations[i] = int(d)
+        cfg = self._cfg = _decoder_config(vocoder, sr, in_channels=in_channels, upsample_initial_channel=upsample_initial_channel,
+                                          gin_channels=gin_channels, upsample_rates=upsample_rates,
+                                          upsample_kernel_sizes=upsample_kernel_sizes, res_kernel_sizes=res_kernel_sizes,
+                                          res_dilations=res_dilations, weight_storage=weight_storage)
         self._h = c_void_p()
         self.vocoder = vocoder
         _check(_lib.rvc_decoder_create(ctypes.byref(cfg), ctypes.byref(self._h)), "rvc_decoder_create")
@@ -1141,8 +1163,17 @@ class Decoder:
         _check(_lib.rvc_decoder_set_tap(self._h, stage, tap.data_ptr() if tap is not None else None),
                "rvc_decoder_set_tap")
 
+    def window_margin(self) -> int:
+        """Input frames on each side that an output frame depends on (rvc_decoder_window_margin); -1: RefineGAN, not covered."""
+        frames = c_int()
+        _check(_lib.rvc_decoder_window_margin(ctypes.byref(self._cfg), ctypes.byref(frames)), "rvc_decoder_window_margin")
+        return frames.value
+
     def forward(self, z: torch.Tensor, f0: torch.Tensor, g: torch.Tensor, *, src_randn: torch.Tensor,
-                src_rand: torch.Tensor | None = None, adain_randn: torch.Tensor | None = None) -> torch.Tensor:
+                src_rand: torch.Tensor | None = None, adain_randn: torch.Tensor | None = None,
+                keep: tuple | None = None) -> torch.Tensor:
+        """keep = (lo, hi) in frames: only the samples [lo * upp, hi * upp) of the waveform, from the same full-length inputs
+        (rvc_decoder_forward_window: the conv stack runs over those frames plus window_margin() on each side)."""
         z, f0, g = _dev_f32(z, "z"), _dev_f32(f0, "f0"), _dev_f32(g, "g")
         b, _, t = z.shape
         noise = DecoderNoise()
@@ -1154,10 +1185,17 @@ class Decoder:
         if adain_randn is not None:
             adain_randn = _dev_f32(adain_randn, "adain_randn")
             noise.adain_randn_dev = adain_randn.data_ptr()
-        out = torch.empty((b, 1, t * self.upp), dtype=torch.float32, device=z.device)
         need = c_size_t()
         _check(_lib.rvc_decoder_workspace_bytes(self._h, b, t, ctypes.byref(need)), "rvc_decoder_workspace_bytes")
         ws = _ws.get("decoder", need.value, z.device)
+        if keep is not None:
+            lo, hi = int(keep[0]), int(keep[1])
+            out = torch.empty((b, 1, max(hi - lo, 0) * self.upp), dtype=torch.float32, device=z.device)
+            _check(_lib.rvc_decoder_forward_window(self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
+                                                   lo, hi, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "rvc_decoder_forward_window")
+            return out
+        out = torch.empty((b, 1, t * self.upp), dtype=torch.float32, device=z.device)
         _check(_lib.rvc_decoder_forward(self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
                                         out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "rvc_decoder_forward")
         return out

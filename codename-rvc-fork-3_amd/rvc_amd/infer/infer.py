@@ -47,6 +47,7 @@ class VoiceConverter:
         self.loaded_model = None
         self.dec_weight_dtype = "f32"   # "bf16": the vocoder's conv weights are stored as bf16 in HBM (BASELINE cfg 4)
         self.dec_arithmetic = "exact"   # "fp16x2": the vocoder's 128- / 256-channel ResBlock convs on error-corrected fp16 pairs (faster, ~2^-22 per product); not with dec_weight_dtype = "bf16"
+        self.trim_vocoder_pad = True    # the vocoder skips the padded second on each side that Pipeline.pipeline trims off again (rvc_decoder_forward_window); False: the whole padded segment (A/B runs)
         self.branch_streams = 0         # Decoder.set_branch_parallel for convert_batch: 0 = every vocoder launch on the utterance's stream, -1 = one side stream per ResBlock branch
 
     # ---- embedder (infer.py:64-74; file layout rvc/lib/utils.py:96-146) ----
@@ -120,6 +121,8 @@ class VoiceConverter:
             if audio_max > 1:
                 audio /= audio_max
         file_index = index_path.strip().strip('"').strip("\n").strip('"').strip().replace("trained", "added")
+
+        self.vc.trim_vocoder_pad = bool(self.trim_vocoder_pad)
 
         def run(chunk):
             return self.vc.pipeline(model=self.hubert_model, net_g=self.net_g, sid=sid, audio=chunk, pitch=pitch,

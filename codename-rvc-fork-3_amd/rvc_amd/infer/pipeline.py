@@ -217,6 +217,9 @@ class Pipeline:
         self._coarse_thr = torch.from_numpy(self._coarse_thresholds()).to(self.device)
         self.index_search = "exact"   # "ivf": search faiss .index files the reference's way (nprobe lists); see FeatureIndex
         self.debug_taps = None     # tests: a dict here receives "f0_raw" and "salience" of the last call (device tensors)
+        # the vocoder only synthesises what survives the [t_pad_tgt:-t_pad_tgt] trim below (+ its receptive field); False: the whole
+        # padded segment, as the reference does (VoiceConverter.trim_vocoder_pad sets it)
+        self.trim_vocoder_pad = True
         self.ref_freqs = REF_FREQS
         self.autotune = Autotune(self.ref_freqs)
         self.note_dict = self.autotune.note_dict
@@ -344,8 +347,9 @@ class Pipeline:
         feats = F.interpolate(feats.permute(0, 2, 1), scale_factor=2).permute(0, 2, 1)
         return feats, feats0, n_audio
 
-    def _synthesize(self, net_g, sid, feats, feats0, n_audio, pitch, pitchf, protect, noise):
-        """pipeline.py:466-490: length bookkeeping, protect blend, net_g.infer."""
+    def _synthesize(self, net_g, sid, feats, feats0, n_audio, pitch, pitchf, protect, noise, trim=0):
+        """pipeline.py:466-490: length bookkeeping, protect blend, net_g.infer.  ``trim`` > 0: return ``seg[trim:-trim]`` of the
+        segment instead, synthesising only the frames those samples lie in where the vocoder allows it."""
         p_len = min(n_audio // self.window, feats.shape[1])
         pitch, pitchf = pitch[:, :p_len], pitchf[:, :p_len]
         if protect < 0.5:  # pipeline.py:474-481
@@ -356,8 +360,17 @@ class Pipeline:
             feats = feats * pitchff.unsqueeze(-1) + feats0 * (1 - pitchff.unsqueeze(-1))
             feats = feats.to(feats0.dtype)
         p_len_t = torch.full((1,), p_len, device=self.device, dtype=torch.long)
-        return net_g.infer(feats.float(), p_len_t, pitch, pitchf.float(), sid, noise=noise,
-                           phone_lengths_host=[p_len])[0][0, 0]
+        upp = getattr(net_g, "upp", 0)
+        n_out = p_len * upp
+        window = (trim > 0 and self.trim_vocoder_pad and self.debug_taps is None and upp > 0 and n_out > 2 * trim and feats.shape[1] == p_len
+                  and getattr(net_g, "vocoder", None) != "RefineGAN")
+        if not window:
+            seg = net_g.infer(feats.float(), p_len_t, pitch, pitchf.float(), sid, noise=noise, phone_lengths_host=[p_len])[0][0, 0]
+            return seg[trim:-trim] if trim > 0 else seg
+        keep_lo, keep_hi = trim // upp, -((trim - n_out) // upp)   # the frames that hold samples [trim, n_out - trim)
+        seg = net_g.infer(feats.float(), p_len_t, pitch, pitchf.float(), sid, noise=noise, phone_lengths_host=[p_len],
+                          keep_frames=(keep_lo, keep_hi))[0][0, 0]
+        return seg[trim - keep_lo * upp: n_out - trim - keep_lo * upp]
 
     def voice_conversion(self, model, net_g, sid, audio0, pitch, pitchf, index, big_npy, index_rate, version, protect,
                          noise=None, as_tensor=False):
@@ -517,8 +530,8 @@ class Pipeline:
                 if noise_seed is not None:
                     for _ in range(12):  # transformers' HuBERT LayerDrop draws, made per segment before the synthesizer's
                         torch.rand([])
-                seg = self._synthesize(net_g, sid, feats, feats0, n_audio, pitch[:, ps], pitchf[:, ps], protect, noise)
-                audio_opt.append(seg[self.t_pad_tgt: -self.t_pad_tgt])
+                audio_opt.append(self._synthesize(net_g, sid, feats, feats0, n_audio, pitch[:, ps], pitchf[:, ps], protect, noise,
+                                                  trim=self.t_pad_tgt))
         out = torch.cat(audio_opt) if len(audio_opt) > 1 else audio_opt[0]
         if volume_envelope != 1:  # pipeline.py:682-685 (both rates are passed as 16000 there, too)
             out = AudioProcessor.change_rms(audio, self.sample_rate, out, self.sample_rate, volume_envelope)

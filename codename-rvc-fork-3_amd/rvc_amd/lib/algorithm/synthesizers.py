@@ -144,7 +144,10 @@ class Synthesizer:
 
     @torch.no_grad()
     def infer(self, phone, phone_lengths, pitch=None, nsff0=None, sid=None, rate=None, noise=None, *,
-              phone_lengths_host=None):
+              phone_lengths_host=None, keep_frames=None):
+        """keep_frames = (lo, hi): the caller only uses the samples of frames [lo, hi) (Pipeline trims its padding off), so the
+        vocoder only synthesises those (Decoder.forward's ``keep``); every noise tensor is still drawn at its full length, in
+        the same order.  Ignored with ``rate`` (the full path)."""
         if self.dec is None:
             raise RuntimeError("Synthesizer.infer before load_state_dict(...).to('cuda:N')")
         w = self.w
@@ -164,5 +167,5 @@ class Synthesizer:
         z = flow_reverse(w, z_p, x_mask, g, half=self.inter_channels // 2, hidden=self.hidden_channels, full=full)
         o = self.dec.forward((z * x_mask).contiguous(), nsff0.float().contiguous(), g[:, :, 0].contiguous(),
                              src_randn=nz["src_randn"].contiguous(), src_rand=nz.get("src_rand"),
-                             adain_randn=nz.get("adain_randn"))
+                             adain_randn=nz.get("adain_randn"), keep=keep_frames if rate is None else None)
         return o, x_mask, (z, z_p, m_p, logs_p)

@@ -271,6 +271,28 @@ int rvc_decoder_forward(rvc_decoder *dec, const float *z_dev, const float *f0_de
                         const rvc_decoder_noise *noise, int batch, int64_t n_frames, float *out_dev,
                         void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The pipeline pads every segment with x_pad seconds of reflected audio, runs the model on the padded clip and trims the pad off the
+ * waveform again (rvc/infer/pipeline.py: `audio_pad = np.pad(audio, (self.t_pad, self.t_pad), mode="reflect")` ...
+ * `[self.t_pad_tgt : -self.t_pad_tgt]`).  After the source module the NSF / MRF vocoder (hifigan_nsf.py:173-207) is a stack of
+ * convolutions with a short receptive field, so the samples that are kept do not depend on most of the padded frames.
+ *
+ * rvc_decoder_window_margin: *frames = the number of input frames on EACH side of an output frame that it can depend on through z or
+ * the source samples, derived layer by layer from the configuration (conv_pre, each transposed conv and its noise conv, the widest
+ * ResBlock branch per stage, conv_post; rounded up to whole frames): 10 for 48 k (rates 12,10,2,2), 11 for 40 k and 32 k.  A pure
+ * host function: no handle, no device.  RefineGAN (interpolated source, a down path) is not covered: *frames = -1.
+ *
+ * rvc_decoder_forward_window: rvc_decoder_forward's samples [keep_lo * upp, keep_hi * upp) -- equal up to fp32 rounding -- into
+ * out_dev [batch, (keep_hi - keep_lo) * upp], from the SAME full-length inputs (z_dev [batch, in_channels, n_frames], f0_dev, the noise
+ * tensors at their full lengths).  The sine phase is a running sum over every earlier frame, so the phase carry still comes from
+ * the whole contour; the source samples and every conv only run over frames [max(0, keep_lo - margin), min(n_frames, keep_hi + margin)).
+ * 0 <= keep_lo < keep_hi <= n_frames; (0, n_frames) makes exactly rvc_decoder_forward's launches.  The workspace of
+ * rvc_decoder_workspace_bytes(dec, batch, n_frames) is sufficient.  An error for a RefineGAN handle and while a debug tap is set
+ * (rvc_decoder_set_tap): use rvc_decoder_forward for those. */
+int rvc_decoder_window_margin(const rvc_decoder_config *cfg, int *frames);
+int rvc_decoder_forward_window(rvc_decoder *dec, const float *z_dev, const float *f0_dev, const float *g_dev,
+                               const rvc_decoder_noise *noise, int batch, int64_t n_frames, int64_t keep_lo, int64_t keep_hi,
+                               float *out_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* Per-handle scheduling hint (see rvc_set_concurrency_hint); 0 = follow the process-wide default.  May be called while
  * forwards of this handle are running on other threads: it only affects forwards that start afterwards. */
 int rvc_decoder_set_concurrency_hint(rvc_decoder *dec, int utterances_in_flight);
