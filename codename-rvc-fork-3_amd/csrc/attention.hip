@@ -19,8 +19,6 @@
 // for 1024 SIMDs, so a layer takes about one wave's time.  K/V of a head (2 x 409 KB) stay in L2.
 #include <stdlib.h>
 
-#include <mutex>
-
 #include "common.h"
 
 namespace rvc {
@@ -656,41 +654,34 @@ extern "C" int rvc_attention_qkv_f32(const float *qkv_dev, const float *emb_rel_
         q.tiles_per_split = (int)ceil_div(ceil_div(n_frames, 32), q.n_splits);
         q.part_o = (float *)workspace_dev; q.part_ml = (float *)((char *)workspace_dev + off_ml); q.frag = (char *)workspace_dev + off_frag;
         hipStream_t st = (hipStream_t)stream;
-        static std::once_flag once;
-        static hipError_t err = hipSuccess;
-        std::call_once(once, [] {
-            err = hipFuncSetAttribute((const void *)attention_bf_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-#ifdef RVC_ABLATE
-            hipFuncSetAttribute((const void *)attention_bf_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-            hipFuncSetAttribute((const void *)attention_bf_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-            hipFuncSetAttribute((const void *)attention_bf_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-            hipFuncSetAttribute((const void *)attention_bf_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-            hipFuncSetAttribute((const void *)attention_bf_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-            hipFuncSetAttribute((const void *)attention_bf_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-#endif
-        });
-        if (err != hipSuccess) return fail("rvc_attention_qkv_f32: cannot reserve the CU's LDS: %s", hipGetErrorString(err));
         const unsigned n_tiles = (unsigned)ceil_div(n_frames, 32);
-        hipLaunchKernelGGL(attention_pack_kv_kernel, dim3(n_tiles, (unsigned)(n_heads * batch)), dim3(512), 0, st, qkv_dev, (unsigned char *)q.frag, q.T, n_heads);
-        RVC_LAUNCH_CHECK();
         const dim3 bgrid((unsigned)ceil_div(n_frames, 32 * ABF_NW), (unsigned)(n_heads * batch), (unsigned)q.n_splits);
+        const auto run = [&](auto kernel) -> int {
+            if (reserve_whole_cu((const void *)kernel, "rvc_attention_qkv_f32")) return 1;   // owns its CU (common.h)
+            hipLaunchKernelGGL(attention_pack_kv_kernel, dim3(n_tiles, (unsigned)(n_heads * batch)), dim3(512), 0, st, qkv_dev, (unsigned char *)q.frag, q.T, n_heads);
+            RVC_LAUNCH_CHECK();
+            hipLaunchKernelGGL(kernel, bgrid, dim3(512), LDS_WHOLE_CU, st, q);
+            RVC_LAUNCH_CHECK();
+            return 0;
+        };
         int dbg = 0;
 #ifdef RVC_ABLATE
         static const int dbg_knob = knob("RVC_ATT_DBG", 0);
         dbg = dbg_knob;
 #endif
+        int rc;
         switch (dbg) {
 #ifdef RVC_ABLATE
-            case 1: hipLaunchKernelGGL(attention_bf_kernel<1>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
-            case 2: hipLaunchKernelGGL(attention_bf_kernel<2>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
-            case 4: hipLaunchKernelGGL(attention_bf_kernel<4>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
-            case 8: hipLaunchKernelGGL(attention_bf_kernel<8>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
-            case 16: hipLaunchKernelGGL(attention_bf_kernel<16>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
-            case 7: hipLaunchKernelGGL(attention_bf_kernel<7>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;
+            case 1: rc = run(attention_bf_kernel<1>); break;
+            case 2: rc = run(attention_bf_kernel<2>); break;
+            case 4: rc = run(attention_bf_kernel<4>); break;
+            case 8: rc = run(attention_bf_kernel<8>); break;
+            case 16: rc = run(attention_bf_kernel<16>); break;
+            case 7: rc = run(attention_bf_kernel<7>); break;
 #endif
-            default: hipLaunchKernelGGL(attention_bf_kernel<0>, bgrid, dim3(512), LDS_WHOLE_CU, st, q); break;   // owns its CU (common.h)
+            default: rc = run(attention_bf_kernel<0>); break;
         }
-        RVC_LAUNCH_CHECK();
+        if (rc) return 1;
         if (q.n_splits > 1) {
             const int64_t work = (int64_t)n_heads * q.T * (64 / 4);
             hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)ceil_div(work, 256), (unsigned)batch), dim3(256), 0, st,

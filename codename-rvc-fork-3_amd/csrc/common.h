@@ -52,14 +52,23 @@ static inline constexpr int knob(const char *, int dflt) { return dflt; }
 // stand-alone, bare bf16 matrix loops do NOT do it, cause still not isolated), so co-residence of the two kernel families is
 // excluded by construction instead of by the sizes their LDS layouts happen to have.
 constexpr int LDS_WHOLE_CU = 163840;
-// ... and this is how a launcher obtains it: once per kernel (registry in error.cpp), then `hipLaunchKernelGGL(k, grid, block, LDS_WHOLE_CU, ...)`.
-// Returns non-zero and sets the error when the attribute cannot be set.
-int reserve_whole_cu(const void *kernel, const char *what);
+
+// ---- one-time GPU resources are kept PER DEVICE ----------------------------------------------------------
+// A process may drive several devices, one host thread per device, with the device current on the calling thread.  Whatever
+// the library sets or uploads once -- a kernel's dynamic-LDS limit, the built-in tables of logmel.hip / filtfilt.hip, the CU
+// count -- is therefore looked up by hipGetDevice under a lock, never held in a per-process static.
+//
+// A launcher that needs more than the default 64 KiB of dynamic LDS (or LDS_WHOLE_CU) calls this before every launch, then
+// `hipLaunchKernelGGL(k, grid, block, bytes, ...)`.  The registry (error.cpp) is keyed by (current device, kernel), remembers
+// the largest byte count granted and sets the attribute only when asked for more.  Returns non-zero and sets the error
+// "<what>: cannot reserve ..." when THIS call's attribute cannot be set; nothing is sticky.
+int reserve_lds(const void *kernel, int bytes, const char *what);
+static inline int reserve_whole_cu(const void *kernel, const char *what) { return reserve_lds(kernel, LDS_WHOLE_CU, what); }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// compute units of the device that was current at the first call (256 when the query fails)
+// compute units of the current device (256 when the query fails)
 int cu_count();
 
 // The grid of a persistent kernel that owns its CU and walks n_tiles tiles: XCD x (workgroup id & 7) owns the contiguous range

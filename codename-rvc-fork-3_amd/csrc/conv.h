@@ -138,7 +138,6 @@ int launch_wino_conv(const float *x, const void *u, bool u_bf16, const float *bi
 // regular conv weight [c_out][c_in][k] -> [3 ceil(k/3)][c_in / 2][c_out][2] (zero taps appended, channel pairs interleaved)
 void wino_pack_host(const float *w_host, int c_out, int c_in, int k, std::vector<float> *out);
 void wino_pack_host_bf16(const float *w_host, int c_out, int c_in, int k, std::vector<uint32_t> *out);   // one word per channel pair
-int wino_pack_weight(const float *w_host, int c_out, int c_in, int k, float **out_dev);
 
 // the same 7- / 11-tap layers on the bf16 matrix cores with fp32 operands split exactly into three bf16 (winobf.hip)
 bool winobf_enabled();   // RVC_WINOBF != 0 (conv.hip)
@@ -146,7 +145,6 @@ bool winobf_supported(int c_in, int c_out, int k, int dil);
 bool winobf_fits(int c_in, int c_out, int64_t L);
 size_t winobf_weight_bytes(int c_out, int c_in, int k);
 void winobf_pack_host(const float *w_host, int c_out, int c_in, int k, std::vector<uint16_t> *out);
-int winobf_pack_weight(const float *w_host, int c_out, int c_in, int k, void **out_dev);
 int launch_winobf_conv(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch,
                        int c_in, int c_out, int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
 // ... with one transform point per wave (winobf2.hip): the form launch_winobf_conv takes unless the ablation build's
@@ -156,8 +154,7 @@ bool winobf2_supported(int c_in, int c_out, int k, int dil);
 int launch_winobf2_conv(const float *x, const void *u, const float *bias, const float *res, const float *accin, float *y, int batch,
                         int c_in, int c_out, int64_t L, int k, int dil, float slope, float out_scale, hipStream_t stream);
 
-// host-side repacks (return freshly hipMalloc'ed device buffers)
-// regular conv weight [c_out][c_in][k] -> [k][c_in][c_out]
-int pack_conv_weight(const float *w_host, int c_out, int c_in, int k, float **out_dev);
+// regular conv weight [c_out][c_in][k] -> the direct form's slab [k][c_in][c_out] (conv.hip)
+void conv_pack_host(const float *w_host, int c_out, int c_in, int k, std::vector<float> *out);
 
 }  // namespace rvc

@@ -499,19 +499,11 @@ int launch_conv(const ConvParams &p_in, hipStream_t stream) {
     }
 }
 
-int pack_conv_weight(const float *w_host, int c_out, int c_in, int k, float **out_dev) {
-    const size_t n = (size_t)c_out * c_in * k;
-    std::string err;
-    float *tmp = (float *)malloc(n * sizeof(float));
-    if (!tmp) return fail("out of host memory");
+void conv_pack_host(const float *w_host, int c_out, int c_in, int k, std::vector<float> *out) {
+    out->resize((size_t)c_out * c_in * k);
     for (int co = 0; co < c_out; ++co)
         for (int ci = 0; ci < c_in; ++ci)
-            for (int t = 0; t < k; ++t) tmp[((size_t)t * c_in + ci) * c_out + co] = w_host[((size_t)co * c_in + ci) * k + t];
-    hipError_t e = hipMalloc((void **)out_dev, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(*out_dev, tmp, n * sizeof(float), hipMemcpyHostToDevice);
-    free(tmp);
-    if (e != hipSuccess) return fail("pack_conv_weight: %s", hipGetErrorString(e));
-    return 0;
+            for (int t = 0; t < k; ++t) (*out)[((size_t)t * c_in + ci) * c_out + co] = w_host[((size_t)co * c_in + ci) * k + t];
 }
 
 }  // namespace rvc
@@ -527,14 +519,9 @@ extern "C" int rvc_set_concurrency_hint(int utterances_in_flight) {
 extern "C" int rvc_conv1d_pack_weight(const float *w_host, int c_out, int c_in, int k, float *w_packed_dev,
                                       void *stream) {
     if (!w_host || !w_packed_dev || c_out <= 0 || c_in <= 0 || k <= 0) return fail("rvc_conv1d_pack_weight: bad argument");
-    float *tmp = nullptr;
-    if (pack_conv_weight(w_host, c_out, c_in, k, &tmp)) return 1;
-    hipError_t e = hipMemcpyAsync(w_packed_dev, tmp, (size_t)c_out * c_in * k * sizeof(float), hipMemcpyDeviceToDevice,
-                                  (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail("rvc_conv1d_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    std::vector<float> packed;
+    conv_pack_host(w_host, c_out, c_in, k, &packed);
+    return upload_packed("rvc_conv1d_pack_weight", packed.data(), packed.size() * sizeof(float), w_packed_dev, stream);
 }
 
 extern "C" int rvc_conv1d_forward(const float *x_dev, const float *w_packed_dev, const float *bias_dev,

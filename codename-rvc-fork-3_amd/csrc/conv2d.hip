@@ -14,7 +14,6 @@
 // epilogue.
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -280,12 +279,7 @@ template <int WM, int WN, int NT, int TAPS>
 static int conv2d_launch(const Conv2dParams &p, hipStream_t stream) {
     constexpr int BM = 32 * WM, BN = 32 * NT * WN;
     const size_t lds = conv2d_lds_bytes<WM, WN, NT, TAPS>();
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [lds] {
-        err = hipFuncSetAttribute((const void *)conv2d_mfma_kernel<WM, WN, NT, TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (err != hipSuccess) return fail("conv2d: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(err));
+    if (reserve_lds((const void *)conv2d_mfma_kernel<WM, WN, NT, TAPS>, (int)lds, "conv2d")) return 1;
     const int th = BN / p.W;
     dim3 grid((unsigned)(ceil_div(p.H, th) * (p.m_pad / BM)), (unsigned)p.batch, (unsigned)p.split);
     hipLaunchKernelGGL((conv2d_mfma_kernel<WM, WN, NT, TAPS>), grid, dim3(256), lds, stream, p);

@@ -18,27 +18,19 @@ struct HostTensor {
     int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
 };
 
-struct DevBuf {
-    float *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int upload(const std::vector<float> &h) {
+template <typename T>
+struct DevBufT {
+    T *p = nullptr;
+    ~DevBufT() { if (p) (void)hipFree(p); }
+    int upload(const std::vector<T> &h) {
         if (p) { (void)hipFree(p); p = nullptr; }
-        hipError_t e = hipMalloc((void **)&p, h.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-        return e == hipSuccess ? 0 : fail("device upload of %zu floats failed: %s", h.size(), hipGetErrorString(e));
+        hipError_t e = hipMalloc((void **)&p, h.size() * sizeof(T));
+        if (e == hipSuccess) e = hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+        return e == hipSuccess ? 0 : fail("device upload of %zu %zu-byte values failed: %s", h.size(), sizeof(T), hipGetErrorString(e));
     }
 };
-
-struct DevBuf16 {
-    uint16_t *p = nullptr;
-    ~DevBuf16() { if (p) (void)hipFree(p); }
-    int upload(const std::vector<uint16_t> &h) {
-        if (p) { (void)hipFree(p); p = nullptr; }
-        hipError_t e = hipMalloc((void **)&p, h.size() * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMemcpy(p, h.data(), h.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-        return e == hipSuccess ? 0 : fail("device upload of %zu bf16 values failed: %s", h.size(), hipGetErrorString(e));
-    }
-};
+using DevBuf = DevBufT<float>;
+using DevBuf16 = DevBufT<uint16_t>;   // bf16 / fp16 bit patterns
 
 struct ConvW {
     DevBuf w, b;

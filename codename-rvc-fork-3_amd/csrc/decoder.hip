@@ -443,11 +443,8 @@ int need(const rvc_decoder *d, const std::string &name, const HostTensor **out, 
 int build_conv(const rvc_decoder *d, const std::string &prefix, int c_out, int c_in, int k, bool bias, ConvW *out, bool as_bf16) {
     const HostTensor *w, *b;
     if (need(d, prefix + ".weight", &w, {c_out, c_in, k})) return 1;
-    std::vector<float> packed((size_t)c_out * c_in * k);
-    for (int co = 0; co < c_out; ++co)
-        for (int ci = 0; ci < c_in; ++ci)
-            for (int t = 0; t < k; ++t)
-                packed[((size_t)t * c_in + ci) * c_out + co] = w->data[((size_t)co * c_in + ci) * k + t];
+    std::vector<float> packed;
+    conv_pack_host(w->data.data(), c_out, c_in, k, &packed);
     if (as_bf16) {   // HBM copy in bf16 (round to nearest even; exact when the caller hands over bf16-valued weights)
         std::vector<uint16_t> half(packed.size());
         for (size_t i = 0; i < packed.size(); ++i) half[i] = bf16_rne(packed[i]);

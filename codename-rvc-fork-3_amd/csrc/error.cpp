@@ -1,8 +1,9 @@
 // Thread-local last-error string behind the C ABI (include/rvc_amd.h: rvc_last_error), and the host helpers common.h declares.
 #include <stdarg.h>
 
+#include <map>
 #include <mutex>
-#include <unordered_set>
+#include <unordered_map>
 
 #include "common.h"
 
@@ -25,28 +26,36 @@ int fail(const char *fmt, ...) {
     return 1;
 }
 
-// common.h: LDS_WHOLE_CU.  One hipFuncSetAttribute per (device, kernel) and process: the attribute belongs to the CURRENT device's
-// function object, so a process that drives several devices (a thread per device) needs it on each.
-int reserve_whole_cu(const void *kernel, const char *what) {
-    static std::mutex mu;
-    static std::unordered_set<const void *> done[64];
+// What the library learns or sets once per DEVICE (common.h), keyed by hipGetDevice on the calling thread: a kernel attribute
+// belongs to the current device's function object, so a process that drives several devices (a thread per device) needs it on each.
+namespace {
+struct DeviceState {
+    int cus = 0;                                       // 0: not asked yet
+    std::unordered_map<const void *, int> lds;         // kernel -> largest dynamic-LDS byte count granted so far
+};
+std::mutex g_dev_mu;
+std::map<int, DeviceState> g_dev;
+}  // namespace
+
+int reserve_lds(const void *kernel, int bytes, const char *what) {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-    std::lock_guard<std::mutex> g(mu);
-    if (dev < 64 && done[dev].count(kernel)) return 0;
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    if (e != hipSuccess) return fail("%s: cannot reserve %d bytes of LDS on device %d: %s", what, LDS_WHOLE_CU, dev, hipGetErrorString(e));
-    if (dev < 64) done[dev].insert(kernel);   // (beyond 64 devices: set it every time -- it is cheap)
+    RVC_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    int &granted = g_dev[dev].lds[kernel];
+    if (bytes <= granted) return 0;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail("%s: cannot reserve %d bytes of LDS on device %d: %s", what, bytes, dev, hipGetErrorString(e));
+    granted = bytes;
     return 0;
 }
 
 int cu_count() {
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-        return cus > 0 ? cus : 256;
-    }();
-    return n;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    DeviceState &d = g_dev[dev];
+    if (!d.cus) d.cus = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0 ? cus : 256;
+    return d.cus;
 }
 
 int upload_packed(const char *fn, const void *host, size_t bytes, void *dev, void *stream) {

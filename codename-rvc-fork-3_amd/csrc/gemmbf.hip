@@ -16,7 +16,6 @@
 // made a 64-cycle chain); two waves per SIMD, and the staging of the next steps placed between the matrix instructions.
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
 
 #include "conv.h"
@@ -276,37 +275,28 @@ gemmbf_kernel(const GemmBfParams p) {
 }
 
 static int gemmbf_launch(GemmBfParams p, hipStream_t stream) {
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [] {
-        err = hipFuncSetAttribute((const void *)gemmbf_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, GBF_LDS);
-        if (err == hipSuccess) err = hipFuncSetAttribute((const void *)gemmbf_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, GBF_LDS);
-    });
-    if (err != hipSuccess) return fail("gemm bf16x3: cannot reserve %d bytes of LDS: %s", GBF_LDS, hipGetErrorString(err));
     p.n_col_blocks = (int)ceil_div(p.N, GBF_BN);
     const int n_m = p.M / GBF_BM;
     dim3 grid((unsigned)(ceil_div(p.n_col_blocks, 8) * 8 * n_m), 1, (unsigned)p.batch);
-#ifdef RVC_ABLATE
-    static const int dbg = knob("RVC_GBF_DBG", 0);
-    if (dbg && p.x_mode == 1) {
-        auto go = [&](auto k) { (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, GBF_LDS); hipLaunchKernelGGL(k, grid, dim3(GBF_NTH), GBF_LDS, stream, p); };
-        switch (dbg) {
-            case 1: go(gemmbf_kernel<1, 1>); break;
-            case 2: go(gemmbf_kernel<1, 2>); break;
-            case 3: go(gemmbf_kernel<1, 3>); break;
-            case 4: go(gemmbf_kernel<1, 4>); break;
-            case 8: go(gemmbf_kernel<1, 8>); break;
-            case 7: go(gemmbf_kernel<1, 7>); break;
-            default: go(gemmbf_kernel<1, 0>); break;
-        }
+    const auto go = [&](auto kernel) -> int {
+        if (reserve_lds((const void *)kernel, GBF_LDS, "gemm bf16x3")) return 1;
+        hipLaunchKernelGGL(kernel, grid, dim3(GBF_NTH), GBF_LDS, stream, p);
         RVC_LAUNCH_CHECK();
         return 0;
+    };
+#ifdef RVC_ABLATE
+    static const int dbg = knob("RVC_GBF_DBG", 0);
+    if (dbg && p.x_mode == 1) switch (dbg) {
+        case 1: return go(gemmbf_kernel<1, 1>);
+        case 2: return go(gemmbf_kernel<1, 2>);
+        case 3: return go(gemmbf_kernel<1, 3>);
+        case 4: return go(gemmbf_kernel<1, 4>);
+        case 8: return go(gemmbf_kernel<1, 8>);
+        case 7: return go(gemmbf_kernel<1, 7>);
+        default: return go(gemmbf_kernel<1, 0>);
     }
 #endif
-    if (p.x_mode == 0) hipLaunchKernelGGL(gemmbf_kernel<0>, grid, dim3(GBF_NTH), GBF_LDS, stream, p);
-    else hipLaunchKernelGGL(gemmbf_kernel<1>, grid, dim3(GBF_NTH), GBF_LDS, stream, p);
-    RVC_LAUNCH_CHECK();
-    return 0;
+    return p.x_mode == 0 ? go(gemmbf_kernel<0>) : go(gemmbf_kernel<1>);
 }
 
 // W [M][K] row-major fp32 (conv: K = taps * c_in with k = tap * c_in + ci) -> [M / 128][K / 16][32-row block 4][split 3][lane 64][8] bf16

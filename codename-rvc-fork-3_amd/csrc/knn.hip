@@ -20,8 +20,6 @@
 // d2 = ||x||^2 - 2 q.x + ||q||^2 is faiss' own BLAS formulation (IndexFlat, > 20 queries), clamped at 0.
 #include <stdlib.h>
 
-#include <mutex>
-
 #include "knn_common.h"
 
 namespace rvc {
@@ -617,28 +615,17 @@ extern "C" int rvc_knn_search(const float *index_dev, const void *aux_dev, int64
     dim3 grid((unsigned)ceil_div(n_queries, plan.q_tile), (unsigned)plan.stripes);
     static const int pf = knob("RVC_KNN_STREAM_PF", 3);
     if (plan.direct) {
-        const size_t lds = knd_lds_bytes(dim);
-        static std::mutex lds_mutex;               // several host threads search concurrently (convert_batch)
-        static size_t lds_set = 0;
-        {
-            std::lock_guard<std::mutex> guard(lds_mutex);
-            if (lds > lds_set) {
-                hipError_t e = hipFuncSetAttribute((const void *)knn_direct_kernel<KND_WAVES, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return fail("rvc_knn_search: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                lds_set = lds;
-            }
-        }
+        const size_t lds = knd_lds_bytes(dim);   // grows with dim: the registry keeps the largest count granted (common.h)
         static const int waves_env = knob("RVC_KNN_DIRECT_WAVES", 0);
         if (waves_env == 84) {   // RVC_KNN_DIRECT_WAVES=84: 4 line groups in flight (+1.5 % on a 2 M-row index)
-            static std::once_flag set84;
-            std::call_once(set84, [lds] {
-                (void)hipFuncSetAttribute((const void *)knn_direct_kernel<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            });
+            if (reserve_lds((const void *)knn_direct_kernel<8, 4>, (int)lds, "rvc_knn_search")) return 1;
             hipLaunchKernelGGL((knn_direct_kernel<8, 4>), grid, dim3(512), lds, (hipStream_t)stream, index_dev, norms_dev,
                                n_rows, dim, queries_dev, n_queries, plan.stripe_rows, part_d, part_id, n_slots);
-        } else
-        hipLaunchKernelGGL((knn_direct_kernel<KND_WAVES, 3>), grid, dim3(KND_WAVES * 64), lds, (hipStream_t)stream, index_dev, norms_dev,
-                           n_rows, dim, queries_dev, n_queries, plan.stripe_rows, part_d, part_id, n_slots);
+        } else {
+            if (reserve_lds((const void *)knn_direct_kernel<KND_WAVES, 3>, (int)lds, "rvc_knn_search")) return 1;
+            hipLaunchKernelGGL((knn_direct_kernel<KND_WAVES, 3>), grid, dim3(KND_WAVES * 64), lds, (hipStream_t)stream, index_dev, norms_dev,
+                               n_rows, dim, queries_dev, n_queries, plan.stripe_rows, part_d, part_id, n_slots);
+        }
     } else if (plan.stream && pf == 2)
         hipLaunchKernelGGL(knn_stream_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, index_dev, norms_dev, n_rows, dim,
                            queries_dev, n_queries, plan.stripe_rows, part_d, part_id, n_slots);

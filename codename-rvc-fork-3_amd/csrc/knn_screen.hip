@@ -35,8 +35,6 @@
 #include <limits.h>
 #include <stdlib.h>
 
-#include <mutex>
-
 #include "knn_common.h"
 
 namespace rvc {
@@ -768,22 +766,6 @@ int knn_screened_search(const float *index, const void *aux_dev, int64_t n_rows,
     int *cnt = (int *)(ws + s.cnt);
     int *cand = (int *)(ws + s.cand);
 
-    static std::once_flag lds_once;
-    static hipError_t lds_err = hipSuccess;
-    std::call_once(lds_once, [] {
-        auto reserve = [](const void *fn, size_t bytes) {
-            if (lds_err == hipSuccess) lds_err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        };
-        static_assert(ScreenTile<2, 64>::LDS_BYTES <= LDS_WHOLE_CU, "");
-        reserve((const void *)knn_screen_glds_kernel<true>, LDS_WHOLE_CU);      // fp16 matrix instructions: these own their CU (common.h)
-        reserve((const void *)knn_screen_glds_kernel<false>, LDS_WHOLE_CU);
-        reserve((const void *)knn_screen_kernel<true, 2, 64>, LDS_WHOLE_CU);
-        reserve((const void *)knn_screen_kernel<false, 2, 64>, LDS_WHOLE_CU);
-        reserve((const void *)knn_screen_kernel<true, 1, 32>, ScreenTile<1, 32>::LDS_BYTES);
-        reserve((const void *)knn_screen_kernel<false, 1, 32>, ScreenTile<1, 32>::LDS_BYTES);
-    });
-    if (lds_err != hipSuccess) return fail("knn screen: cannot reserve LDS: %s", hipGetErrorString(lds_err));
-
     hipLaunchKernelGGL(knn_to_half_kernel, dim3((unsigned)ceil_div(n_queries, 4)), dim3(256), 0, stream, queries, n_queries, dim, qh,
                        (float *)nullptr, qstat, (unsigned *)nullptr, mins, s.sample_tiles * s.slots_per_tile, cnt);
     RVC_LAUNCH_CHECK();
@@ -798,44 +780,42 @@ int knn_screened_search(const float *index, const void *aux_dev, int64_t n_rows,
     // sample pass: one tile per block, tiles sample_step apart
     p.n_stripes = s.sample_tiles; p.tiles_per_block = 1; p.tile_step = s.sample_step;
     unsigned blocks = (unsigned)(ceil_div(p.n_stripes, 8) * 8 * p.n_qtiles);
-    auto launch = [&](bool append, unsigned nblocks) {
-#define RVC_SCREEN(AP, W, K)                                                                                               \
-    hipLaunchKernelGGL((knn_screen_kernel<AP, W, K>), dim3(nblocks), dim3((ScreenTile<W, K>::THREADS)),                   \
-                       ((W) == 2 ? (size_t)LDS_WHOLE_CU : (size_t)ScreenTile<W, K>::LDS_BYTES), stream, p)
+    static_assert(ScreenTile<2, 64>::LDS_BYTES <= LDS_WHOLE_CU, "");
+    const auto launch = [&](bool append, unsigned nblocks) -> int {
+        const auto go = [&](auto kernel, int threads, int lds) -> int {
+            if (reserve_lds((const void *)kernel, lds, "knn screen")) return 1;
+            hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(threads), lds, stream, p);
+            RVC_LAUNCH_CHECK();
+            return 0;
+        };
+        // fp16 matrix instructions: the two-wave-row tiles own their CU (common.h)
+#define RVC_SCREEN(AP, W, K) go(knn_screen_kernel<AP, W, K>, ScreenTile<W, K>::THREADS, (W) == 2 ? LDS_WHOLE_CU : (int)ScreenTile<W, K>::LDS_BYTES)
         static const int glds_env = knob("RVC_KNN_GLDS", 0);   // 1: the LDS-DMA staged variant (measured equal: 0.555 vs 0.545 ms)
-        if (s.wm == 2 && s.bk == 64 && glds_env) {
-            if (append) hipLaunchKernelGGL(knn_screen_glds_kernel<true>, dim3(nblocks), dim3(512), LDS_WHOLE_CU, stream, p);
-            else hipLaunchKernelGGL(knn_screen_glds_kernel<false>, dim3(nblocks), dim3(512), LDS_WHOLE_CU, stream, p);
-        } else if (s.wm == 2 && s.bk == 64) {
+        if (s.wm == 2 && s.bk == 64 && glds_env)
+            return append ? go(knn_screen_glds_kernel<true>, 512, LDS_WHOLE_CU) : go(knn_screen_glds_kernel<false>, 512, LDS_WHOLE_CU);
+        if (s.wm == 2 && s.bk == 64) {
 #ifdef RVC_ABLATE
             static const int dbg = knob("RVC_KNN_DBG", 0);
-            if (append && dbg) {
-#define RVC_SCREEN_DBG(D) hipLaunchKernelGGL((knn_screen_kernel<true, 2, 64, D>), dim3(nblocks), dim3(512), (ScreenTile<2, 64>::LDS_BYTES), stream, p)
-                auto res = [](const void *fn) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ScreenTile<2, 64>::LDS_BYTES); };
-                switch (dbg) {
-#define RVC_SD(D) case D: res((const void *)knn_screen_kernel<true, 2, 64, D>); RVC_SCREEN_DBG(D); break
-                    RVC_SD(32); RVC_SD(34); RVC_SD(48); RVC_SD(50); RVC_SD(54); RVC_SD(36); RVC_SD(40);
+            if (append) switch (dbg) {
+#define RVC_SD(D) case D: return go(knn_screen_kernel<true, 2, 64, D>, 512, (int)ScreenTile<2, 64>::LDS_BYTES)
+                RVC_SD(32); RVC_SD(34); RVC_SD(48); RVC_SD(50); RVC_SD(54); RVC_SD(36); RVC_SD(40);
 #undef RVC_SD
-                    default: RVC_SCREEN(true, 2, 64); break;
-                }
-#undef RVC_SCREEN_DBG
-            } else
+                default: break;
+            }
 #endif
-            if (append) RVC_SCREEN(true, 2, 64); else RVC_SCREEN(false, 2, 64);
+            return append ? RVC_SCREEN(true, 2, 64) : RVC_SCREEN(false, 2, 64);
         }
-        else { if (append) RVC_SCREEN(true, 1, 32); else RVC_SCREEN(false, 1, 32); }
+        return append ? RVC_SCREEN(true, 1, 32) : RVC_SCREEN(false, 1, 32);
 #undef RVC_SCREEN
     };
-    launch(false, blocks);
-    RVC_LAUNCH_CHECK();
+    if (launch(false, blocks)) return 1;
     hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)ceil_div(n_queries, 4)), dim3(256), 0, stream, mins, p.n_slots, qstat,
                        (const unsigned *)(ab + aux.stats), n_queries, thr);
     RVC_LAUNCH_CHECK();
     // main pass over every row
     p.n_stripes = s.n_stripes; p.tiles_per_block = s.tiles_per_block; p.tile_step = 1;
     blocks = (unsigned)(ceil_div(p.n_stripes, 8) * 8 * p.n_qtiles);
-    launch(true, blocks);
-    RVC_LAUNCH_CHECK();
+    if (launch(true, blocks)) return 1;
     return knn_finalize_launch(index, n_rows, dim, queries, n_queries, cand, cnt, nullptr, aux_dev, s.cap, out_d2, out_ids,
                                cnt + n_queries, stream);
 }

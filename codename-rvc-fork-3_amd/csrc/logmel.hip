@@ -29,17 +29,21 @@ struct LogmelTables {
     int *mel_count = nullptr;      // [128]
     float *mel_w = nullptr;        // [128][max_count]
     int max_count = 0;
-    bool ready = false;
+    int device = -1;               // the device the pointers live on
 };
-static LogmelTables g_tab;
 static std::mutex g_tab_mutex;
+static std::vector<LogmelTables> g_tabs;   // one per device that has run the front end (filtfilt.hip's tables: the same)
 
 static double hz_to_mel_htk(double f) { return 2595.0 * log10(1.0 + f / 700.0); }
 static double mel_to_hz_htk(double m) { return 700.0 * (pow(10.0, m / 2595.0) - 1.0); }
 
-static int build_tables() {
+// the current device's tables, built and uploaded when the device is first seen
+static int tables_for_device(LogmelTables *out) {
+    LogmelTables tab;
+    RVC_HIP(hipGetDevice(&tab.device));
     std::lock_guard<std::mutex> lock(g_tab_mutex);
-    if (g_tab.ready) return 0;
+    for (const LogmelTables &t : g_tabs)
+        if (t.device == tab.device) { *out = t; return 0; }
     // DFT basis, double -> float
     std::vector<float> basis((size_t)LM_NFFT * LM_ROWS, 0.f);
     for (int n = 0; n < LM_NFFT; ++n)
@@ -87,14 +91,15 @@ static int build_tables() {
         if (e == hipSuccess) e = hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice);
         return e;
     };
-    hipError_t e = up(basis.data(), basis.size() * 4, (void **)&g_tab.basis);
-    if (e == hipSuccess) e = up(window.data(), window.size() * 4, (void **)&g_tab.window);
-    if (e == hipSuccess) e = up(start.data(), start.size() * 4, (void **)&g_tab.mel_start);
-    if (e == hipSuccess) e = up(count.data(), count.size() * 4, (void **)&g_tab.mel_count);
-    if (e == hipSuccess) e = up(mel_w.data(), mel_w.size() * 4, (void **)&g_tab.mel_w);
+    hipError_t e = up(basis.data(), basis.size() * 4, (void **)&tab.basis);
+    if (e == hipSuccess) e = up(window.data(), window.size() * 4, (void **)&tab.window);
+    if (e == hipSuccess) e = up(start.data(), start.size() * 4, (void **)&tab.mel_start);
+    if (e == hipSuccess) e = up(count.data(), count.size() * 4, (void **)&tab.mel_count);
+    if (e == hipSuccess) e = up(mel_w.data(), mel_w.size() * 4, (void **)&tab.mel_w);
     if (e != hipSuccess) return fail("logmel: table upload failed: %s", hipGetErrorString(e));
-    g_tab.max_count = max_count;
-    g_tab.ready = true;
+    tab.max_count = max_count;
+    g_tabs.push_back(tab);
+    *out = tab;
     return 0;
 }
 
@@ -323,21 +328,22 @@ extern "C" int rvc_logmel_rmvpe(const float *audio_dev, int batch, int64_t n_sam
     size_t need = 0;
     if (rvc_logmel_workspace_bytes(batch, n_samples, &need)) return 1;
     if (workspace_bytes < need) return fail("rvc_logmel_rmvpe: workspace too small (%zu < %zu)", workspace_bytes, need);
-    if (!g_tab.ready && build_tables()) return 1;
+    LogmelTables tab;
+    if (tables_for_device(&tab)) return 1;
     hipStream_t stream = (hipStream_t)stream_;
     float *F = (float *)workspace_dev;
     float *C = (float *)((char *)workspace_dev + align_up((size_t)batch * LM_NFFT * T * 4, 256));
     hipLaunchKernelGGL(logmel_frames_kernel, dim3((unsigned)ceil_div(T, 256), LM_NFFT, batch), dim3(256), 0, stream, audio_dev,
-                       n_samples, g_tab.window, T, F);
+                       n_samples, tab.window, T, F);
     RVC_LAUNCH_CHECK();
     ConvParams p;
     p.x1 = F; p.c1 = LM_NFFT; p.slope1 = 1.f; p.x1_bstride = (int64_t)LM_NFFT * T; p.l_in = T;
-    p.w = g_tab.basis;
+    p.w = tab.basis;
     p.y = C; p.y_bstride = (int64_t)LM_ROWS * T; p.m_total = LM_ROWS; p.c_out = LM_ROWS; p.n_cols = T; p.l_out = T;
     p.kw = 1; p.dil = 1; p.padl = 0; p.batch = batch;
     if (launch_conv(p, stream)) return 1;
     hipLaunchKernelGGL(logmel_mel_kernel, dim3((unsigned)ceil_div(n_frames_padded, 256), LM_MELS, batch), dim3(256), 0, stream, C,
-                       T, n_frames_padded, g_tab.mel_start, g_tab.mel_count, g_tab.mel_w, g_tab.max_count, mel_dev);
+                       T, n_frames_padded, tab.mel_start, tab.mel_count, tab.mel_w, tab.max_count, mel_dev);
     RVC_LAUNCH_CHECK();
     return 0;
 }

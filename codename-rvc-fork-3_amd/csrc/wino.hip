@@ -29,7 +29,6 @@
 // like conv.hip's.  What shaped the loop is written at the kernel.
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
 
 #include "conv.h"
@@ -513,12 +512,7 @@ static int wino_launch_cfg(WinoParams p, hipStream_t stream) {
     p.sb_per_block = BNT / p.dil;
     p.n_sb = ceil_div(p.L, (int64_t)4 * p.dil);
     const size_t lds = wino_lds_bytes<KW, WM, WN, CIC, WB16, R>();
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [lds] {
-        err = hipFuncSetAttribute((const void *)wino_conv_kernel<KW, WM, WN, CIC, DBG, WB16, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
-    if (err != hipSuccess) return fail("wino conv: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(err));
+    if (reserve_lds((const void *)wino_conv_kernel<KW, WM, WN, CIC, DBG, WB16, R>, (int)lds, "wino conv")) return 1;
     p.n_tile_blocks = (int)ceil_div(p.n_sb, p.sb_per_block);
     const int n_m = p.c_out / (32 * WM);
     dim3 grid((unsigned)(ceil_div(p.n_tile_blocks, 8) * 8 * n_m), 1, (unsigned)p.batch);
@@ -632,30 +626,16 @@ void wino_pack_host_bf16(const float *w_host, int c_out, int c_in, int k, std::v
     for (size_t i = 0; i < out->size(); ++i) (*out)[i] = (uint32_t)bf16_rne(f[2 * i]) | ((uint32_t)bf16_rne(f[2 * i + 1]) << 16);
 }
 
-int wino_pack_weight(const float *w_host, int c_out, int c_in, int k, float **out_dev) {
-    if (c_in % 2) return fail("wino_pack_weight: odd c_in %d", c_in);
-    std::vector<float> u;
-    wino_pack_host(w_host, c_out, c_in, k, &u);
-    hipError_t e = hipMalloc((void **)out_dev, u.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(*out_dev, u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail("wino_pack_weight: %s", hipGetErrorString(e));
-    return 0;
-}
-
 }  // namespace rvc
 
 using namespace rvc;
 
 extern "C" int rvc_conv1d_wino_pack_weight(const float *w_host, int c_out, int c_in, int k, float *u_dev, void *stream) {
     if (!w_host || !u_dev || c_out <= 0 || c_in <= 0 || !(k == 3 || k == 7 || k == 11)) return fail("rvc_conv1d_wino_pack_weight: bad argument");
-    float *tmp = nullptr;
-    if (wino_pack_weight(w_host, c_out, c_in, k, &tmp)) return 1;
-    const size_t bytes = (size_t)3 * ((k + 2) / 3) * c_in * c_out * sizeof(float);
-    hipError_t e = hipMemcpyAsync(u_dev, tmp, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail("rvc_conv1d_wino_pack_weight: %s", hipGetErrorString(e));
-    return 0;
+    if (c_in % 2) return fail("wino_pack_weight: odd c_in %d", c_in);
+    std::vector<float> u;
+    wino_pack_host(w_host, c_out, c_in, k, &u);
+    return upload_packed("rvc_conv1d_wino_pack_weight", u.data(), u.size() * sizeof(float), u_dev, stream);
 }
 
 extern "C" int rvc_conv1d_wino_forward(const float *x_dev, const float *u_dev, const float *bias_dev, const float *res_dev,

@@ -61,7 +61,6 @@
 //     LDS latency / DMA issue per step are exposed.  What remains is the per-step synchronisation, not the chain.
 #include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -562,12 +561,7 @@ static int winobf_launch(WinoBfParams p, hipStream_t stream) {
     using GM = WbfGeom<KW, BM, BNT>;
     p.sb_per_block = (BNT - (GM::G - 1) * p.dil) / p.dil;   // valid tiles + the (G - 1) d windows behind them = BNT transformed windows
     p.n_sb = ceil_div(p.L, (int64_t)4 * p.dil);
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [] {
-        err = hipFuncSetAttribute((const void *)winobf_conv_kernel<KW, DBG, BM, BNT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    });
-    if (err != hipSuccess) return fail("winobf conv: cannot reserve %d bytes of LDS: %s", GM::LDS_BYTES, hipGetErrorString(err));
+    if (reserve_whole_cu((const void *)winobf_conv_kernel<KW, DBG, BM, BNT>, "winobf conv")) return 1;
     p.n_tile_blocks = (int)ceil_div(p.n_sb, p.sb_per_block);
     const int n_m = p.c_out / BM;
     dim3 grid((unsigned)(ceil_div(p.n_tile_blocks, 8) * 8 * n_m), 1, (unsigned)p.batch);
@@ -694,16 +688,6 @@ void winobf_pack_host(const float *w_host, int c_out, int c_in, int k, std::vect
                                     (*out)[piece * 512 + lane * 8 + e] = s[sp];
                                 }
                             }
-}
-
-int winobf_pack_weight(const float *w_host, int c_out, int c_in, int k, void **out_dev) {
-    if (!winobf_supported(c_in, c_out, k, 1)) return fail("winobf_pack_weight: unsupported shape");
-    std::vector<uint16_t> u;
-    winobf_pack_host(w_host, c_out, c_in, k, &u);
-    hipError_t e = hipMalloc(out_dev, u.size() * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMemcpy(*out_dev, u.data(), u.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail("winobf_pack_weight: %s", hipGetErrorString(e));
-    return 0;
 }
 
 }  // namespace rvc

@@ -29,7 +29,6 @@
 // x 3 products = 3.0 cost more matrix work than this form's 0.477 x 6 = 2.86).
 #include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -725,15 +724,9 @@ winobf2_conv_kernel(const Wbf2Params p) {
 
 template <int KW, int BM, int DBG = 0>
 static int winobf2_launch(Wbf2Params p, hipStream_t stream) {
-    using GM = W2Geom<KW, BM>;
     p.sb_per_block = W2_BNT / p.dil;   // every accumulator column a valid tile: the (G - 1) d windows behind the 64 are the loader wave's
     const int64_t n_sb = ceil_div(p.L, (int64_t)4 * p.dil);
-    static std::once_flag once;
-    static hipError_t err = hipSuccess;
-    std::call_once(once, [] {
-        err = hipFuncSetAttribute((const void *)winobf2_conv_kernel<KW, BM, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_WHOLE_CU);
-    });
-    if (err != hipSuccess) return fail("winobf2 conv: cannot reserve %d bytes of LDS: %s", GM::LDS_BYTES, hipGetErrorString(err));
+    if (reserve_whole_cu((const void *)winobf2_conv_kernel<KW, BM, DBG>, "winobf2 conv")) return 1;
     p.n_tile_blocks = (int)ceil_div(n_sb, p.sb_per_block);
     const int n_m = p.c_out / BM;
     dim3 grid((unsigned)(ceil_div(p.n_tile_blocks, 8) * 8 * n_m), 1, (unsigned)p.batch);

@@ -17,6 +17,9 @@
  *     rvc_decoder_forward only READS the handle (weights, tables) and works in the caller's workspace, so several threads
  *     may run forwards of one handle concurrently, each with its own stream and workspace (VoiceConverter.convert_batch
  *     does); create / set_tensor / finalize / set_tap / destroy must not overlap any other call on the same handle;
+ *   - a process may drive several devices, one host thread per device, with that device current on the calling thread for
+ *     every call (the handles and *_dev pointers it passes live there).  What the library sets or uploads once -- kernel
+ *     attributes, its built-in tables -- is kept per device;
  *   - tensors are dense, row-major, fp32 unless said otherwise.
  */
 #ifndef RVC_AMD_H
