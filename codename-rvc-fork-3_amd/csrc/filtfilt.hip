@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "iir5.h"   // FiltCoef, ff_step and the LDS tile movement, shared with preprocess.hip (K17)
 
 // SciPy's C loop is built without FMA; HIP's __dmul_rn/__dadd_rn are plain operators that clang would contract
 // (default -ffp-contract=fast), and a 1-ulp change is amplified ~1e5x by this recurrence: contraction off for the file.
@@ -27,14 +28,7 @@
 
 namespace rvc {
 
-constexpr int FF_ORD = 5;
 constexpr int FF_PAD = 18;   // 3 * max(len(a), len(b))
-
-struct FiltCoef {
-    double b[FF_ORD + 1];
-    double a[FF_ORD + 1];
-    double zi[FF_ORD];
-};
 
 // forward pass input: odd extension of x; backward pass input: the forward output reversed.  Branch-free: one
 // unconditional load from a clamped index, the odd reflection applied afterwards (a load inside a divergent branch is
@@ -51,36 +45,12 @@ __device__ __forceinline__ double ff_input(const double *__restrict__ x, int64_t
     return (left || right) ? 2.0 * edge - v : v;
 }
 
-__device__ __forceinline__ double ff_step(const FiltCoef &c, double xv, double z[FF_ORD]) {
-#pragma clang fp contract(off)
-    // scipy/signal/_lfilter.c.src: y = z0 + b0*x;  z_i = z_{i+1} + x*b_{i+1} - y*a_{i+1};  z_last = x*b_n - y*a_n
-    // plain operators under contract(off): the __dmul_rn/__dadd_rn helpers are ordinary operators that clang fuses.
-    // Same operations and operand order as SciPy's, written so that only three of the 21 are on the step-to-step
-    // dependency chain (y, y*a1, z0): a float64 VALU result takes ~25 cycles to come back, and the straightforward
-    // order (mul, dependent add, mul, dependent add, ...) made every one of them wait -- 550 cycles per sample.
-    double xb[FF_ORD + 1], t[FF_ORD], ya[FF_ORD];
-#pragma unroll
-    for (int i = 0; i <= FF_ORD; ++i) xb[i] = xv * c.b[i];          // independent of the state
-    const double y = z[0] + xb[0];
-#pragma unroll
-    for (int i = 0; i < FF_ORD - 1; ++i) t[i] = z[i + 1] + xb[i + 1];   // independent of y
-#pragma unroll
-    for (int i = 0; i < FF_ORD; ++i) ya[i] = y * c.a[i + 1];
-#pragma unroll
-    for (int i = 0; i < FF_ORD - 1; ++i) z[i] = t[i] - ya[i];
-    z[FF_ORD - 1] = xb[FF_ORD] - ya[FF_ORD - 1];
-    return y;
-}
-
 // One wave = 64 consecutive chunks, one lane per chunk.  A lane walks its chunk sequentially, so a naive load touches
 // 64 different cache lines per step; instead the wave moves data in [64 chunks] x [32 steps] tiles through LDS: tile
 // rows are fetched as contiguous 256-byte pieces (two chunk rows per load instruction), one step-block ahead of the
 // recurrence, and the outputs of a step-block leave the same way.  Per-step cost drops from ~470 cycles (0.9 ms per
-// pass) to the float64 VALU work of the recurrence itself.
+// pass) to the float64 VALU work of the recurrence itself.  (FF_SB, FF_TS and the tile helpers: iir5.h)
 // forward pass -> yf[ne]; backward pass -> out[n] (reversed back and cropped)
-constexpr int FF_SB = 32;              // steps per tile
-constexpr int FF_TS = FF_SB + 1;       // tile row stride in doubles (conflict-free ds_read_b64 down a column)
-
 __global__ void __launch_bounds__(64)
 ff_chunk_kernel(const double *__restrict__ x, int64_t n, const double *yf_in, int backward, FiltCoef c, int chunk,
                 int warm, int64_t n_chunks, double *yf_out, double *__restrict__ out, const double *__restrict__ zstate) {
@@ -146,8 +116,7 @@ ff_chunk_kernel(const double *__restrict__ x, int64_t n, const double *yf_in, in
         // (lds_barrier, not __syncthreads: the latter also waits for every outstanding global access -- i.e. for the acknowledgement of
         // the previous step-block's 32 output stores, ~7 000 cycles per step-block, as long as the recurrence itself)
         lds_barrier();                                // previous tile fully consumed (single wave: a cheap fence)
-#pragma unroll
-        for (int k = 0; k < 32; ++k) tin[(2 * k + hrow) * FF_TS + u] = r[k];
+        ff_tile_put_rows(tin, r, hrow, u);
         if (sb + 1 < n_sb) fetch(sb + 1);
         lds_barrier();
         const int64_t ib = w0 + (int64_t)sb * FF_SB;
@@ -157,14 +126,10 @@ ff_chunk_kernel(const double *__restrict__ x, int64_t n, const double *yf_in, in
 #pragma unroll
             for (int s8 = 0; s8 < FF_SB; s8 += 8) {
                 double xin[8], yo[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) xin[q] = tin[lane * FF_TS + s8 + q];
+                ff_tile_get8(tin, lane, s8, xin);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) yo[q] = ff_step(c, xin[q], z);
-                if (emit) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) tout[lane * FF_TS + s8 + q] = yo[q];
-                }
+                if (emit) ff_tile_put8(tout, lane, s8, yo);
             }
         } else {
             // a step-block that crosses either end of the extended signal for some lane (the first wave's warm-up,
@@ -176,8 +141,7 @@ ff_chunk_kernel(const double *__restrict__ x, int64_t n, const double *yf_in, in
                 const int64_t ia = ib + s8;
                 if (ia < 0 || ia >= ne) continue;                 // per lane: nothing to do in this batch
                 double xin[8], yo[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) xin[q] = tin[lane * FF_TS + s8 + q];
+                ff_tile_get8(tin, lane, s8, xin);
                 if (ia + 7 < ne) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) yo[q] = ff_step(c, xin[q], z);
@@ -192,17 +156,13 @@ ff_chunk_kernel(const double *__restrict__ x, int64_t n, const double *yf_in, in
                         for (int k = 0; k < FF_ORD; ++k) z[k] = ia + q < ne ? zn[k] : z[k];
                     }
                 }
-                if (emit) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) tout[lane * FF_TS + s8 + q] = yo[q];
-                }
+                if (emit) ff_tile_put8(tout, lane, s8, yo);
             }
         }
         if (sb >= out_sb0) {                          // uniform: the last chunk / FF_SB step-blocks carry outputs
             lds_barrier();
             double yv[32];                            // read unconditionally: an LDS read inside the bounds check below is waited for
-#pragma unroll                                        // before the branch closes -- 32 serial round trips per step-block, as long as the recurrence
-            for (int k = 0; k < 32; ++k) yv[k] = tout[(2 * k + hrow) * FF_TS + u];
+            ff_tile_get_rows(tout, yv, hrow, u);          // before the branch closes -- 32 serial round trips per step-block, as long as the recurrence
 #pragma unroll
             for (int k = 0; k < 32; ++k) {
                 const int64_t row_ch = ch0 + 2 * k + hrow;

@@ -175,6 +175,12 @@ SYMBOLS = {
     "rvc_kmeans_assign": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rvc_kmeans_update": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    "rvc_lfilter_order5_warmup": (c_int, [c_void_p, POINTER(c_int64)]),
+    "rvc_lfilter_order5_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rvc_frame_rms_frames": (c_int, [c_int64, c_int64, c_int64, POINTER(c_int64), POINTER(c_size_t)]),
+    "rvc_frame_rms_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "rvc_slice_export_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                     c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -472,6 +478,90 @@ def filtfilt_order5(x: torch.Tensor, b, a) -> torch.Tensor:
     _check(_lib.rvc_filtfilt_order5(x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr(), ws.data_ptr(),
                                     ws.numel(), _stream()), "rvc_filtfilt_order5")
     return y
+
+
+# ---- K17 -----------------------------------------------------------------------------------------
+def _lfilter_coef(b, a):
+    import numpy as np
+    b = np.asarray(b, dtype=np.float64)
+    a = np.asarray(a, dtype=np.float64)
+    if b.shape != (6,) or a.shape != (6,):
+        raise NativeError("lfilter_order5 wants b[6], a[6]")
+    return np.ascontiguousarray(np.concatenate([b, a]))
+
+
+def lfilter_warmup(b, a) -> int:
+    """The warm-up (samples) rvc_lfilter_order5_f64 runs in front of every chunk for these coefficients."""
+    coef, warm = _lfilter_coef(b, a), c_int64()
+    _check(_lib.rvc_lfilter_order5_warmup(coef.ctypes.data, ctypes.byref(warm)), "rvc_lfilter_order5_warmup")
+    return warm.value
+
+
+def lfilter_order5(x: torch.Tensor, b, a) -> torch.Tensor:
+    """scipy.signal.lfilter(b, a, x) (zero initial state) for a 5th-order filter; x: 1-D float64 on the device."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float64 or x.dim() != 1:
+        raise NativeError("lfilter_order5 wants a 1-D float64 HBM tensor")
+    x = x.contiguous()
+    coef = _lfilter_coef(b, a)
+    y = torch.empty_like(x)
+    if x.numel() == 0:               # an empty tensor has no storage to point at; the coefficients are still checked
+        lfilter_warmup(b, a)
+        return y
+    with torch.cuda.device(x.device):
+        _check(_lib.rvc_lfilter_order5_f64(x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr(), _stream()),
+               "rvc_lfilter_order5_f64")
+    return y
+
+
+def frame_rms(x: torch.Tensor, frame_length: int, hop_length: int) -> torch.Tensor:
+    """get_rms of the reference's slicer.py: x 1-D float64 on the device -> float64 [n_frames] on the device."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float64 or x.dim() != 1:
+        raise NativeError("frame_rms wants a 1-D float64 HBM tensor")
+    x = x.contiguous()
+    n_frames, need = c_int64(), c_size_t()
+    _check(_lib.rvc_frame_rms_frames(x.numel(), int(frame_length), int(hop_length), ctypes.byref(n_frames), ctypes.byref(need)),
+           "rvc_frame_rms_frames")
+    out = torch.empty(n_frames.value, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _ws.get("frame_rms", need.value, x.device)
+        # an empty tensor has no storage: hand the library an address it never dereferences (n == 0 reads nothing)
+        _check(_lib.rvc_frame_rms_f64(x.data_ptr() or ws.data_ptr(), x.numel(), int(frame_length), int(hop_length),
+                                      out.data_ptr() or ws.data_ptr(), n_frames.value, ws.data_ptr(), ws.numel(), _stream()),
+               "rvc_frame_rms_f64")
+    return out
+
+
+def slice_export(x: torch.Tensor, bounds, up: int, down: int, h: torch.Tensor):
+    """Every slice of one file in one launch.  x: 1-D float64 on the device; bounds: [(start, end), ...] half-open sample ranges;
+    h: the FIR of rvc_amd.lib.audio.resample_filter(up, down) on the device.
+    -> (full float32 [sum len], lo float32 [sum ceil(len * up / down)], off_full, off_lo): the two packed device buffers and the
+    n_seg + 1 offsets of every slice in each (Python lists)."""
+    import numpy as np
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 1
+            and torch.is_tensor(h) and h.is_cuda and h.dtype == torch.float64 and h.dim() == 1 and h.device == x.device):
+        raise NativeError("slice_export wants 1-D float64 HBM tensors on one device")
+    x, h = x.contiguous(), h.contiguous()
+    try:
+        tab = np.ascontiguousarray(np.asarray(bounds, dtype=np.int64).reshape(-1, 2))
+    except (TypeError, ValueError, OverflowError) as e:
+        raise NativeError(f"slice_export: bounds must be (start, end) integer pairs ({e})")
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise NativeError(f"slice_export: up = {up}, down = {down} must be at least 1")
+    n_seg = tab.shape[0]
+    length = np.maximum(tab[:, 1] - tab[:, 0], 0)                  # a refused table still gets buffers of a sane size
+    off_full = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+    off_lo = np.concatenate([[0], np.cumsum(-(-(length * up) // down))]).astype(np.int64)
+    tables = torch.from_numpy(np.concatenate([tab.reshape(-1), off_full, off_lo])).to(x.device)
+    full = torch.empty(int(off_full[-1]), dtype=torch.float32, device=x.device)
+    lo = torch.empty(int(off_lo[-1]), dtype=torch.float32, device=x.device)
+    seg_ptr = tables.data_ptr()
+    with torch.cuda.device(x.device):
+        _check(_lib.rvc_slice_export_f32(x.data_ptr() or seg_ptr, x.numel(), tab.ctypes.data, seg_ptr, seg_ptr + 16 * n_seg,
+                                         seg_ptr + 16 * n_seg + 8 * (n_seg + 1), n_seg, up, down, h.data_ptr(), h.numel(),
+                                         full.data_ptr() or seg_ptr, full.numel(), lo.data_ptr() or seg_ptr, lo.numel(), _stream()),
+               "rvc_slice_export_f32")
+    return full, lo, off_full.tolist(), off_lo.tolist()
 
 
 # ---- K5 ------------------------------------------------------------------------------------------

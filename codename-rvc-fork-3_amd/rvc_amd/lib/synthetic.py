@@ -509,3 +509,27 @@ def make_fcpe_checkpoint(seed: int = 0, *, hidden: int = 512, layers: int = 6) -
                 "clip_val": 1e-5},
     }
     return {"config_dict": config, "model": g.out}
+
+
+# ---- the dataset preprocessor's test recording -----------------------------------------------------------------------------
+PREPROCESS_LAYOUT = (("s", 45), ("v", 120), ("s", 30), ("v", 110), ("s", 50), ("v", 130), ("z", 90), ("v", 105), ("s", 20), ("v", 60),
+                     ("s", 40))     # (kind, length in hops of round(sr * 0.015)): s = near-silence, v = voiced, z = digital zero
+
+
+def synth_preprocess_audio(sr: int, seed: int = 11) -> np.ndarray:
+    """Voiced stretches separated by near-silence and one run of zeros, for the slicer of rvc_amd.train.preprocess (float64 that
+    a float32 WAV carries exactly).  Silences dip towards 0.37 of their length, so the slicer's arg-min has one clear answer."""
+    hop = round(sr * 0.015)
+    rng = np.random.default_rng(seed)
+    parts = []
+    for kind, hops in PREPROCESS_LAYOUT:
+        n = hops * hop
+        t = np.arange(n, dtype=np.float64)
+        if kind == "v":
+            parts.append(0.3 * np.sin(2 * np.pi * 220 * t / sr) * (0.6 + 0.4 * np.sin(2 * np.pi * 3 * t / sr))
+                         + 0.01 * rng.standard_normal(n))
+        elif kind == "s":
+            parts.append(1e-3 * (0.25 + np.abs(t - 0.37 * n) / n) * rng.standard_normal(n))
+        else:
+            parts.append(np.zeros(n))
+    return np.concatenate(parts).astype(np.float32).astype(np.float64)

@@ -652,6 +652,42 @@ int rvc_kmeans_update(const float *x_dev, int64_t n_rows, int dim, const int32_t
                       int64_t n_centroids, const float *old_centroids_dev, float *out_centroids_dev, void *workspace_dev,
                       size_t workspace_bytes, void *stream);
 
+/* ---- K17: the dataset preprocessor (csrc/preprocess.hip) ----------------------------------------------------- *
+ * The device steps of rvc/train/preprocess/preprocess.py + slicer.py.  Common contract: every argument is checked on the host
+ * before anything touches the device; sample indices are 64-bit; all launches are asynchronous on `stream`; no atomics, fixed
+ * summation orders: two calls give identical bits.
+ *
+ * rvc_lfilter_order5_f64 replaces `signal.lfilter(self.b_high, self.a_high, audio)` (preprocess.py:146): y = lfilter(b, a, x),
+ *   causal, zero initial state, float64, SciPy's operation sequence without FMA contraction.  coef_host (host memory, 12
+ *   doubles): b[6], a[6] with a[0] == 1 and every pole inside the unit circle.  x_dev, y_dev: [n], n >= 0, must not alias.
+ *   Chunks of 2048 outputs are run side by side, each from a zero state `warm` samples earlier (from sample 0 where that is
+ *   nearer: those chunks are bit-exact); warm = the smallest multiple of 32 with rho^warm <= 2^-53, rho the largest pole
+ *   radius of a[] -- rvc_lfilter_order5_warmup returns it.  Agrees with SciPy to the conditioning of the recurrence
+ *   (csrc/preprocess.hip).
+ * rvc_frame_rms_f64 replaces `get_rms(y, frame_length, hop_length)` (slicer.py:199-235): pad = frame_length / 2 zeros on both
+ *   sides, frame t covers padded samples [t * hop, t * hop + frame_length), n_frames = (n + 2 * pad - frame_length) / hop + 1
+ *   by floor division (0 frames when the padded signal is shorter than a frame), out[t] = sqrt(sum of squares / frame_length).
+ *   frame_length >= 1, hop >= 1, n >= 0; rvc_frame_rms_frames gives n_frames and the workspace for a shape (one double per
+ *   hop-long piece of the padded signal).  Every sample is read once when frame_length is a multiple of hop.
+ * rvc_slice_export_f32 replaces the per-slice `astype(np.float32)` + `librosa.resample(slice, orig_sr=sr, target_sr=16000)`
+ *   pairs of process_audio_segment / simple_cut (preprocess.py:64-126) with one launch per file.  bounds_host (host memory,
+ *   n_seg x 2 int64): half-open sample ranges [start_s, end_s) with 0 <= start_s <= end_s <= n; they may overlap, touch or be
+ *   empty.  seg_dev: the same table in device memory; off_full_dev / off_lo_dev: n_seg + 1 int64 each, the exclusive prefix sums
+ *   of len_s = end_s - start_s and of ceil(len_s * up / down) (last entry = n_full / n_lo, which must match the host table).
+ *     full[off_full[s] + i] = (float)x[start_s + i]                                             (round to nearest)
+ *     lo[off_lo[s] + j]     = (float) sum_m h[m] * xup_s[j * down + (n_taps - 1) / 2 - m],  j < ceil(len_s * up / down)
+ *   xup_s = segment s ALONE zero-stuffed by `up`, zeros outside it: rvc_resample_poly_f64's convention per segment, float64
+ *   accumulation in ascending m.  up, down >= 1, n_taps odd.  A refused call writes nothing. */
+int rvc_lfilter_order5_warmup(const double *coef_host, int64_t *warm);
+int rvc_lfilter_order5_f64(const double *x_dev, int64_t n, const double *coef_host, double *y_dev, void *stream);
+int rvc_frame_rms_frames(int64_t n, int64_t frame_length, int64_t hop, int64_t *n_frames, size_t *workspace_bytes);
+int rvc_frame_rms_f64(const double *x_dev, int64_t n, int64_t frame_length, int64_t hop, double *out_dev, int64_t n_frames,
+                      void *workspace_dev, size_t workspace_bytes, void *stream);
+int rvc_slice_export_f32(const double *x_dev, int64_t n, const int64_t *bounds_host, const int64_t *seg_dev,
+                         const int64_t *off_full_dev, const int64_t *off_lo_dev, int64_t n_seg, int up, int down,
+                         const double *h_dev, int64_t n_taps, float *full_dev, int64_t n_full, float *lo_dev, int64_t n_lo,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
