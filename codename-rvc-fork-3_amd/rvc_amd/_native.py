@@ -3,7 +3,9 @@
 The library is the product: there is no CPU or PyTorch fallback.  If the shared object is
 missing this module raises at import, and every wrapper raises ``NativeError`` with the
 library's own message when a call fails.  Tensors are passed as raw device pointers
-(``tensor.data_ptr()``) and every launch goes on torch's current HIP stream.
+(``tensor.data_ptr()``).  A native call runs on the device of its tensors and on that device's current HIP stream:
+``_call`` makes the device current for the call when it is not, so the caller no longer has to.  The tensors of
+one call share a device, and a ``Decoder`` or ``MelTransform`` handle belongs to the device it was built for.
 """
 from __future__ import annotations
 
@@ -199,7 +201,54 @@ def _check(rc: int, what: str):
 
 
 def _stream() -> int:
+    """The current device's current stream, for code that calls `_lib` directly (the wrappers below go through `_call`)."""
     return torch.cuda.current_stream().cuda_stream
+
+
+def _call(name: str, device: torch.device, *args, stream: bool = True) -> None:
+    """The one path into every entry point that launches on, or sizes for, a device.  The library looks its per-device resources up
+    by hipGetDevice (csrc/common.h), so `device` is made current for the call when it is not already; `device`'s current stream is
+    appended as the trailing `void *stream` argument (stream=False: a size query, which takes none); a non-zero return raises
+    NativeError with the library's message.  The device already being current, the common case, costs one index compare."""
+    if device.index != torch.cuda.current_device():
+        if device.type != "cuda" or device.index is None:
+            raise NativeError(f"{name}: every tensor must live in HBM, got one on {device}")
+        with torch.cuda.device(device):
+            return _call(name, device, *args, stream=stream)
+    if stream:
+        args += (torch.cuda.current_stream(device.index).cuda_stream,)
+    _check(getattr(_lib, name)(*args), name)
+
+
+def _device(*tensors) -> torch.device:
+    """The one device of a call's tensor arguments (None: an optional one that is absent)."""
+    device = None
+    for t in tensors:
+        if t is None:
+            continue
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise NativeError(f"the tensors of one call must share a device, got {device} and {t.device}")
+    return device
+
+
+def _cuda_device(device=None) -> torch.device:
+    """`device` with its index spelled out; None or a bare "cuda" is the current device."""
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise NativeError(f"a HIP device is needed, got {device} (no CPU fallback)")
+    return device if device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _ptr(t):
+    """The address of an optional tensor: NULL when it is absent."""
+    return t.data_ptr() if t is not None else None
+
+
+def _host(w: torch.Tensor) -> torch.Tensor:
+    """A weight as the contiguous fp32 host tensor the *_pack_weight / set_tensor entry points read."""
+    return w.detach().float().cpu().contiguous()
 
 
 def _dev_f32(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -231,15 +280,34 @@ class _Workspace:
 _ws = _Workspace()
 
 
+def _size(query: str, device, *dims) -> int:
+    """What the size query `query`(*dims, &bytes) answers on `device` (some depend on its CU count)."""
+    need = c_size_t()
+    _call(query, device, *dims, ctypes.byref(need), stream=False)
+    return need.value
+
+
+def _workspace(tag: str, device, query: str, *dims) -> torch.Tensor:
+    """The scratch buffer of (tag, device, device's current stream), at least as large as `query`(*dims) asks for."""
+    return _ws.get(tag, _size(query, device, *dims), device)
+
+
+def _pack_slab(stem: str, device, host: tuple, size_dims: tuple, pack_dims: tuple = None) -> torch.Tensor:
+    """<stem>_weight_bytes(*size_dims) -> an int16 slab of that size on `device` -> <stem>_pack_weight(*host tensors, *pack_dims,
+    slab): the host weights (None: an absent one) repacked into the fragment layout a kernel family reads."""
+    device = _cuda_device(device)
+    slab = torch.empty(_size(stem + "_weight_bytes", device, *size_dims) // 2, dtype=torch.int16, device=device)
+    _call(stem + "_pack_weight", device, *(_ptr(w) for w in host), *(size_dims if pack_dims is None else pack_dims), slab.data_ptr())
+    return slab
+
+
 # ---- K1 ------------------------------------------------------------------------------------------
 def knn_index_build(index: torch.Tensor) -> torch.Tensor:
     """The per-index aux blob of rvc_knn_index_build (||x||^2, fp16 copy, screening statistics) as an opaque uint8 tensor."""
     index = _dev_f32(index, "index")
-    need = c_size_t()
-    _check(_lib.rvc_knn_index_aux_bytes(index.shape[0], index.shape[1], ctypes.byref(need)), "rvc_knn_index_aux_bytes")
-    aux = torch.empty(need.value, dtype=torch.uint8, device=index.device)
-    _check(_lib.rvc_knn_index_build(index.data_ptr(), index.shape[0], index.shape[1], aux.data_ptr(), aux.numel(), _stream()),
-           "rvc_knn_index_build")
+    n, d = index.shape[0], index.shape[1]
+    aux = torch.empty(_size("rvc_knn_index_aux_bytes", index.device, n, d), dtype=torch.uint8, device=index.device)
+    _call("rvc_knn_index_build", index.device, index.data_ptr(), n, d, aux.data_ptr(), aux.numel())
     return aux
 
 
@@ -255,17 +323,15 @@ def knn_search(index: torch.Tensor, aux: torch.Tensor, queries: torch.Tensor, k:
     index, queries = _dev_f32(index, "index"), _dev_f32(queries, "queries")
     if not aux.is_cuda or aux.dtype != torch.uint8:
         raise NativeError("aux must be the uint8 HBM blob returned by knn_index_build")
+    dev = _device(index, aux, queries)
     nq = queries.shape[0]
-    d2 = torch.empty((nq, k), dtype=torch.float32, device=index.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=index.device)
+    d2 = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
     if nq == 0:
         return d2, ids
-    need = c_size_t()
-    _check(_lib.rvc_knn_workspace_bytes(index.shape[0], nq, index.shape[1], k, ctypes.byref(need)), "rvc_knn_workspace_bytes")
-    ws = _ws.get("knn", need.value, index.device)
-    _check(_lib.rvc_knn_search(index.data_ptr(), aux.data_ptr(), index.shape[0], index.shape[1], queries.data_ptr(),
-                               nq, k, d2.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-           "rvc_knn_search")
+    ws = _workspace("knn", dev, "rvc_knn_workspace_bytes", index.shape[0], nq, index.shape[1], k)
+    _call("rvc_knn_search", dev, index.data_ptr(), aux.data_ptr(), index.shape[0], index.shape[1], queries.data_ptr(), nq, k,
+          d2.data_ptr(), ids.data_ptr(), ws.data_ptr(), ws.numel())
     return d2, ids
 
 
@@ -275,12 +341,12 @@ def knn_rank_candidates(index: torch.Tensor, aux: torch.Tensor, queries: torch.T
     if not cand.is_cuda or cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != queries.shape[0]:
         raise NativeError("cand must be an int32 HBM tensor [n_queries, cap]")
     cand = cand.contiguous()
+    dev = _device(index, aux, queries, cand)
     nq = queries.shape[0]
-    d2 = torch.empty((nq, k), dtype=torch.float32, device=index.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=index.device)
-    _check(_lib.rvc_knn_rank_candidates(index.data_ptr(), aux.data_ptr(), index.shape[0], index.shape[1], queries.data_ptr(), nq,
-                                        cand.data_ptr(), cand.shape[1], k, d2.data_ptr(), ids.data_ptr(), _stream()),
-           "rvc_knn_rank_candidates")
+    d2 = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    _call("rvc_knn_rank_candidates", dev, index.data_ptr(), aux.data_ptr(), index.shape[0], index.shape[1], queries.data_ptr(), nq,
+          cand.data_ptr(), cand.shape[1], k, d2.data_ptr(), ids.data_ptr())
     return d2, ids
 
 
@@ -288,32 +354,26 @@ def knn_blend(index: torch.Tensor, feats: torch.Tensor, d2: torch.Tensor, ids: t
     index, feats, d2 = _dev_f32(index, "index"), _dev_f32(feats, "feats"), _dev_f32(d2, "d2")
     ids = ids.contiguous()
     out = torch.empty_like(feats)
-    _check(_lib.rvc_knn_blend(index.data_ptr(), index.shape[1], feats.data_ptr(), d2.data_ptr(), ids.data_ptr(),
-                              feats.shape[0], d2.shape[1], float(index_rate), out.data_ptr(), _stream()),
-           "rvc_knn_blend")
+    _call("rvc_knn_blend", _device(index, feats, d2, ids), index.data_ptr(), index.shape[1], feats.data_ptr(), d2.data_ptr(),
+          ids.data_ptr(), feats.shape[0], d2.shape[1], float(index_rate), out.data_ptr())
     return out
 
 
 # ---- K16 -----------------------------------------------------------------------------------------
-def _kmeans_workspace(n_rows: int, n_centroids: int, dim: int, device) -> torch.Tensor:
-    need = c_size_t()
-    _check(_lib.rvc_kmeans_workspace_bytes(n_rows, n_centroids, dim, ctypes.byref(need)), "rvc_kmeans_workspace_bytes")
-    return _ws.get("kmeans", need.value, device)
-
-
 def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
     """-> (ids int32 [n], d2 float32 [n]): the nearest centroid of every row of x and its squared distance (rvc_kmeans_assign)."""
     x, centroids = _dev_f32(x, "x"), _dev_f32(centroids, "centroids")
     if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
         raise NativeError(f"x {tuple(x.shape)} and centroids {tuple(centroids.shape)} must be [n, d] and [k, d]")
+    dev = _device(x, centroids)
     n, d = x.shape
-    ids = torch.empty(n, dtype=torch.int32, device=x.device)
-    d2 = torch.empty(n, dtype=torch.float32, device=x.device)
+    ids = torch.empty(n, dtype=torch.int32, device=dev)
+    d2 = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return ids, d2
-    ws = _kmeans_workspace(n, centroids.shape[0], d, x.device)
-    _check(_lib.rvc_kmeans_assign(x.data_ptr(), n, d, centroids.data_ptr(), centroids.shape[0], ids.data_ptr(), d2.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), _stream()), "rvc_kmeans_assign")
+    ws = _workspace("kmeans", dev, "rvc_kmeans_workspace_bytes", n, centroids.shape[0], d)
+    _call("rvc_kmeans_assign", dev, x.data_ptr(), n, d, centroids.data_ptr(), centroids.shape[0], ids.data_ptr(), d2.data_ptr(),
+          ws.data_ptr(), ws.numel())
     return ids, d2
 
 
@@ -329,10 +389,11 @@ def kmeans_update(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, o
     if n == 0:
         return old.clone()
     order, offsets = order.contiguous(), offsets.contiguous()
+    dev = _device(x, order, offsets, old)
     out = torch.empty_like(old)
-    ws = _kmeans_workspace(n, k, d, x.device)
-    _check(_lib.rvc_kmeans_update(x.data_ptr(), n, d, order.data_ptr(), offsets.data_ptr(), k, old.data_ptr(), out.data_ptr(),
-                                  ws.data_ptr(), ws.numel(), _stream()), "rvc_kmeans_update")
+    ws = _workspace("kmeans", dev, "rvc_kmeans_workspace_bytes", n, k, d)
+    _call("rvc_kmeans_update", dev, x.data_ptr(), n, d, order.data_ptr(), offsets.data_ptr(), k, old.data_ptr(), out.data_ptr(),
+          ws.data_ptr(), ws.numel())
     return out
 
 
@@ -390,26 +451,27 @@ def logmel_rmvpe(audio: torch.Tensor, pad_to: int = 32) -> tuple[torch.Tensor, i
     t = n // 160 + 1
     t_pad = pad_to * ((t - 1) // pad_to + 1) if pad_to > 1 else t
     mel = torch.empty((b, 128, t_pad), dtype=torch.float32, device=audio.device)
-    need = c_size_t()
-    _check(_lib.rvc_logmel_workspace_bytes(b, n, ctypes.byref(need)), "rvc_logmel_workspace_bytes")
-    ws = _ws.get("logmel", need.value, audio.device)
-    _check(_lib.rvc_logmel_rmvpe(audio.data_ptr(), b, n, mel.data_ptr(), t_pad, ws.data_ptr(), ws.numel(), _stream()),
-           "rvc_logmel_rmvpe")
+    ws = _workspace("logmel", audio.device, "rvc_logmel_workspace_bytes", b, n)
+    _call("rvc_logmel_rmvpe", audio.device, audio.data_ptr(), b, n, mel.data_ptr(), t_pad, ws.data_ptr(), ws.numel())
     return mel, t
 
 
 class MelTransform:
-    """Handle on rvc_mel_*: STFT magnitude / log-mel for any (n_fft, hop, window, pad, mel matrix) on the device."""
+    """Handle on rvc_mel_*: STFT magnitude / log-mel for any (n_fft, hop, window, pad, mel matrix) on one device."""
 
-    def __init__(self, n_fft: int, hop: int, win_length: int, pad: int, mel_matrix, mag_eps: float = 0.0, log_floor: float = 1e-5):
+    def __init__(self, n_fft: int, hop: int, win_length: int, pad: int, mel_matrix, mag_eps: float = 0.0, log_floor: float = 1e-5,
+                 device=None):
+        """device: where the handle's tables live and its forwards run (None: the current device)."""
         import numpy as np
         m = np.ascontiguousarray(mel_matrix, dtype=np.float32)
         if m.ndim != 2 or m.shape[1] != n_fft // 2 + 1:
             raise NativeError(f"mel matrix must be [n_mels, {n_fft // 2 + 1}], got {m.shape}")
         self.n_fft, self.hop, self.n_mels, self.bins = n_fft, hop, m.shape[0], n_fft // 2 + 1
+        self.device = _cuda_device(device)
         self._h = c_void_p()
-        _check(_lib.rvc_mel_create(n_fft, hop, win_length, pad, float(mag_eps), float(log_floor), m.ctypes.data, m.shape[0],
-                                   ctypes.byref(self._h)), "rvc_mel_create")
+        with torch.cuda.device(self.device):   # rvc_mel_create allocates and uploads, and takes no stream
+            _check(_lib.rvc_mel_create(n_fft, hop, win_length, pad, float(mag_eps), float(log_floor), m.ctypes.data, m.shape[0],
+                                       ctypes.byref(self._h)), "rvc_mel_create")
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -422,18 +484,17 @@ class MelTransform:
         return t.value
 
     def forward(self, audio: torch.Tensor, want_mel: bool = True, want_spec: bool = False):
-        """audio [B, n] float32 on the device -> (log-mel [B, n_mels, T] or None, magnitude [B, n_fft/2+1, T] or None)."""
+        """audio [B, n] float32 on the handle's device -> (log-mel [B, n_mels, T] or None, magnitude [B, n_fft/2+1, T] or None)."""
         audio = _dev_f32(audio, "audio")
+        dev = self.device
+        if audio.device != dev:
+            raise NativeError(f"MelTransform of {dev} got audio on {audio.device}")
         b, n = audio.shape
         t = self.n_frames(n)
-        mel = torch.empty((b, self.n_mels, t), dtype=torch.float32, device=audio.device) if want_mel else None
-        spec = torch.empty((b, self.bins, t), dtype=torch.float32, device=audio.device) if want_spec else None
-        need = c_size_t()
-        _check(_lib.rvc_mel_workspace_bytes(self._h, b, n, ctypes.byref(need)), "rvc_mel_workspace_bytes")
-        ws = _ws.get("mel", need.value, audio.device)
-        _check(_lib.rvc_mel_forward(self._h, audio.data_ptr(), b, n, mel.data_ptr() if mel is not None else None,
-                                    spec.data_ptr() if spec is not None else None, ws.data_ptr(), ws.numel(), _stream()),
-               "rvc_mel_forward")
+        mel = torch.empty((b, self.n_mels, t), dtype=torch.float32, device=dev) if want_mel else None
+        spec = torch.empty((b, self.bins, t), dtype=torch.float32, device=dev) if want_spec else None
+        ws = _workspace("mel", dev, "rvc_mel_workspace_bytes", self._h, b, n)
+        _call("rvc_mel_forward", dev, self._h, audio.data_ptr(), b, n, _ptr(mel), _ptr(spec), ws.data_ptr(), ws.numel())
         return mel, spec
 
 
@@ -444,8 +505,7 @@ def resample_poly(x: torch.Tensor, up: int, down: int, h: torch.Tensor) -> torch
     x, h = x.contiguous(), h.contiguous()
     n_out = -(-x.numel() * up // down)
     y = torch.empty(n_out, dtype=torch.float64, device=x.device)
-    _check(_lib.rvc_resample_poly_f64(x.data_ptr(), x.numel(), int(up), int(down), h.data_ptr(), h.numel(), y.data_ptr(), n_out,
-                                      _stream()), "rvc_resample_poly_f64")
+    _call("rvc_resample_poly_f64", _device(x, h), x.data_ptr(), x.numel(), int(up), int(down), h.data_ptr(), h.numel(), y.data_ptr(), n_out)
     return y
 
 
@@ -460,7 +520,8 @@ def _filtfilt_coef(b, a):
     if key not in _ff_coef_cache:
         b = np.asarray(b, dtype=np.float64)
         a = np.asarray(a, dtype=np.float64)
-        assert b.shape == (6,) and a.shape == (6,) and a[0] == 1.0
+        if not (b.shape == (6,) and a.shape == (6,) and a[0] == 1.0):
+            raise NativeError("filtfilt_order5 wants b[6], a[6] with a[0] == 1")
         _ff_coef_cache[key] = np.ascontiguousarray(np.concatenate([b, a, signal.lfilter_zi(b, a)]))
     return _ff_coef_cache[key]
 
@@ -472,11 +533,8 @@ def filtfilt_order5(x: torch.Tensor, b, a) -> torch.Tensor:
     x = x.contiguous()
     coef = _filtfilt_coef(b, a)
     y = torch.empty_like(x)
-    need = c_size_t()
-    _check(_lib.rvc_filtfilt_workspace_bytes(x.numel(), ctypes.byref(need)), "rvc_filtfilt_workspace_bytes")
-    ws = _ws.get("filtfilt", need.value, x.device)
-    _check(_lib.rvc_filtfilt_order5(x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), _stream()), "rvc_filtfilt_order5")
+    ws = _workspace("filtfilt", x.device, "rvc_filtfilt_workspace_bytes", x.numel())
+    _call("rvc_filtfilt_order5", x.device, x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr(), ws.data_ptr(), ws.numel())
     return y
 
 
@@ -507,9 +565,7 @@ def lfilter_order5(x: torch.Tensor, b, a) -> torch.Tensor:
     if x.numel() == 0:               # an empty tensor has no storage to point at; the coefficients are still checked
         lfilter_warmup(b, a)
         return y
-    with torch.cuda.device(x.device):
-        _check(_lib.rvc_lfilter_order5_f64(x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr(), _stream()),
-               "rvc_lfilter_order5_f64")
+    _call("rvc_lfilter_order5_f64", x.device, x.data_ptr(), x.numel(), coef.ctypes.data, y.data_ptr())
     return y
 
 
@@ -522,12 +578,10 @@ def frame_rms(x: torch.Tensor, frame_length: int, hop_length: int) -> torch.Tens
     _check(_lib.rvc_frame_rms_frames(x.numel(), int(frame_length), int(hop_length), ctypes.byref(n_frames), ctypes.byref(need)),
            "rvc_frame_rms_frames")
     out = torch.empty(n_frames.value, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        ws = _ws.get("frame_rms", need.value, x.device)
-        # an empty tensor has no storage: hand the library an address it never dereferences (n == 0 reads nothing)
-        _check(_lib.rvc_frame_rms_f64(x.data_ptr() or ws.data_ptr(), x.numel(), int(frame_length), int(hop_length),
-                                      out.data_ptr() or ws.data_ptr(), n_frames.value, ws.data_ptr(), ws.numel(), _stream()),
-               "rvc_frame_rms_f64")
+    ws = _ws.get("frame_rms", need.value, x.device)
+    # an empty tensor has no storage: hand the library an address it never dereferences (n == 0 reads nothing)
+    _call("rvc_frame_rms_f64", x.device, x.data_ptr() or ws.data_ptr(), x.numel(), int(frame_length), int(hop_length),
+          out.data_ptr() or ws.data_ptr(), n_frames.value, ws.data_ptr(), ws.numel())
     return out
 
 
@@ -556,11 +610,9 @@ def slice_export(x: torch.Tensor, bounds, up: int, down: int, h: torch.Tensor):
     full = torch.empty(int(off_full[-1]), dtype=torch.float32, device=x.device)
     lo = torch.empty(int(off_lo[-1]), dtype=torch.float32, device=x.device)
     seg_ptr = tables.data_ptr()
-    with torch.cuda.device(x.device):
-        _check(_lib.rvc_slice_export_f32(x.data_ptr() or seg_ptr, x.numel(), tab.ctypes.data, seg_ptr, seg_ptr + 16 * n_seg,
-                                         seg_ptr + 16 * n_seg + 8 * (n_seg + 1), n_seg, up, down, h.data_ptr(), h.numel(),
-                                         full.data_ptr() or seg_ptr, full.numel(), lo.data_ptr() or seg_ptr, lo.numel(), _stream()),
-               "rvc_slice_export_f32")
+    _call("rvc_slice_export_f32", x.device, x.data_ptr() or seg_ptr, x.numel(), tab.ctypes.data, seg_ptr, seg_ptr + 16 * n_seg,
+          seg_ptr + 16 * n_seg + 8 * (n_seg + 1), n_seg, up, down, h.data_ptr(), h.numel(),
+          full.data_ptr() or seg_ptr, full.numel(), lo.data_ptr() or seg_ptr, lo.numel())
     return full, lo, off_full.tolist(), off_lo.tolist()
 
 
@@ -568,28 +620,22 @@ def slice_export(x: torch.Tensor, bounds, up: int, down: int, h: torch.Tensor):
 def bigru_forward(gi: torch.Tensor, whh_t: torch.Tensor, bhh: torch.Tensor, multi_cu: bool = True) -> torch.Tensor:
     """gi [B,T,2,768] (input projections) -> [B,T,512]; see include/rvc_amd.h."""
     gi, whh_t, bhh = _dev_f32(gi, "gi"), _dev_f32(whh_t, "whh_t"), _dev_f32(bhh, "bhh")
+    dev = _device(gi, whh_t, bhh)
     b, t = gi.shape[0], gi.shape[1]
-    out = torch.empty((b, t, 512), dtype=torch.float32, device=gi.device)
-    ws_ptr, ws_bytes = None, 0
-    if multi_cu:
-        need = c_size_t()
-        _check(_lib.rvc_bigru_workspace_bytes(b, ctypes.byref(need)), "rvc_bigru_workspace_bytes")
-        ws = _ws.get("bigru", need.value, gi.device)
-        ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
-    _check(_lib.rvc_bigru_forward(gi.data_ptr(), whh_t.data_ptr(), bhh.data_ptr(), out.data_ptr(), b, t, 256, ws_ptr,
-                                  ws_bytes, _stream()), "rvc_bigru_forward")
+    out = torch.empty((b, t, 512), dtype=torch.float32, device=dev)
+    ws = _workspace("bigru", dev, "rvc_bigru_workspace_bytes", b) if multi_cu else None
+    _call("rvc_bigru_forward", dev, gi.data_ptr(), whh_t.data_ptr(), bhh.data_ptr(), out.data_ptr(), b, t, 256, _ptr(ws),
+          ws.numel() if multi_cu else 0)
     return out
 
 
 def bigru_redone(batch: int = 1, device=None) -> int:
     """How many (batch item, direction) sequences of the last multi-workgroup forward on the current stream's workspace
     had to be recomputed by the single-workgroup kernel (synchronises the stream)."""
-    device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-    need = c_size_t()
-    _check(_lib.rvc_bigru_workspace_bytes(batch, ctypes.byref(need)), "rvc_bigru_workspace_bytes")
-    ws = _ws.get("bigru", need.value, device)
+    device = _cuda_device(device)
+    ws = _workspace("bigru", device, "rvc_bigru_workspace_bytes", batch)
     n = c_int()
-    _check(_lib.rvc_bigru_status(ws.data_ptr(), batch, ctypes.byref(n), _stream()), "rvc_bigru_status")
+    _call("rvc_bigru_status", device, ws.data_ptr(), batch, ctypes.byref(n))
     return n.value
 
 
@@ -598,57 +644,58 @@ def bigru_set_spin_limit(polls: int) -> None:
 
 
 # ---- HuBERT attention -------------------------------------------------------------------------------
+def _is_f32_hbm(t: torch.Tensor) -> bool:
+    return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
 def attention_qkv(qkv: torch.Tensor, n_heads: int, scale: float, emb_rel_k: torch.Tensor = None,
                   emb_rel_v: torch.Tensor = None) -> torch.Tensor:
     """qkv [B, T, 3 * n_heads * d] (fused projection output, d = 64 or 96) -> softmax(q k^T * scale [+ rel]) v [+ rel]
     as [B, T, n_heads * d].  emb_rel_k / emb_rel_v [21, d]: the TextEncoder's relative-position embeddings."""
-    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.dim() == 3
+    if not (_is_f32_hbm(qkv) and qkv.dim() == 3):
+        raise NativeError("attention_qkv wants a contiguous float32 HBM tensor [B, T, 3 * n_heads * d]")
     b, t, c = qkv.shape
     hd = c // (3 * n_heads)
-    rel = emb_rel_k is not None
-    if rel:
-        for e in (emb_rel_k, emb_rel_v):
-            assert e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and tuple(e.shape) == (21, hd)
-    out = torch.empty(b, t, n_heads * hd, dtype=torch.float32, device=qkv.device)
-    need = c_size_t()
-    _check(_lib.rvc_attention_workspace_bytes(b, t, n_heads, hd, ctypes.byref(need)), "rvc_attention_workspace_bytes")
-    ws = _ws.get("attention", need.value, qkv.device)
-    _check(_lib.rvc_attention_qkv_f32(qkv.data_ptr(), emb_rel_k.data_ptr() if rel else None,
-                                      emb_rel_v.data_ptr() if rel else None, out.data_ptr(), b, t, n_heads, hd,
-                                      float(scale), ws.data_ptr(), ws.numel(), _stream()), "rvc_attention_qkv_f32")
+    rel = (emb_rel_k, emb_rel_v) if emb_rel_k is not None else (None, None)
+    if rel[0] is not None and not all(e is not None and _is_f32_hbm(e) and tuple(e.shape) == (21, hd) for e in rel):
+        raise NativeError(f"attention_qkv wants emb_rel_k and emb_rel_v as contiguous float32 HBM tensors [21, {hd}]")
+    dev = _device(qkv, *rel)
+    out = torch.empty(b, t, n_heads * hd, dtype=torch.float32, device=dev)
+    ws = _workspace("attention", dev, "rvc_attention_workspace_bytes", b, t, n_heads, hd)
+    _call("rvc_attention_qkv_f32", dev, qkv.data_ptr(), _ptr(rel[0]), _ptr(rel[1]), out.data_ptr(), b, t, n_heads, hd, float(scale),
+          ws.data_ptr(), ws.numel())
     return out
 
 
 # ---- RMVPE U-Net conv epilogue ------------------------------------------------------------------------
 def bias_relu_add_(x: torch.Tensor, bias: torch.Tensor = None, res: torch.Tensor = None, relu: bool = True) -> torch.Tensor:
     """In place: x = relu(x + bias[c]) + res for x [B, C, ...] (contiguous, trailing extent a multiple of 4)."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 3
+    if not (_is_f32_hbm(x) and x.dim() >= 3):
+        raise NativeError("bias_relu_add_ wants a contiguous float32 HBM tensor [B, C, ...]")
     b, c = x.shape[0], x.shape[1]
     inner = x.numel() // (b * c)
-    if res is not None:
-        assert res.is_cuda and res.dtype == torch.float32 and res.is_contiguous() and res.shape == x.shape
-    _check(_lib.rvc_bias_relu_add_f32(x.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                      res.data_ptr() if res is not None else None, x.data_ptr(), b, c, inner, int(relu),
-                                      _stream()), "rvc_bias_relu_add_f32")
+    if res is not None and not (_is_f32_hbm(res) and res.shape == x.shape):
+        raise NativeError("bias_relu_add_ wants res as a contiguous float32 HBM tensor of x's shape")
+    _call("rvc_bias_relu_add_f32", _device(x, bias, res), x.data_ptr(), _ptr(bias), _ptr(res), x.data_ptr(), b, c, inner, int(relu))
     return x
 
 
 def rownorm_gelu_(x: torch.Tensor, gamma: torch.Tensor = None, beta: torch.Tensor = None, eps: float = 1e-5) -> torch.Tensor:
     """In place: x = gelu(group_norm(x, num_groups = channels)) for x [B, C, L] (fp32, HBM, contiguous)."""
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+    if not (_is_f32_hbm(x) and x.dim() == 3):
+        raise NativeError("rownorm_gelu_ wants a contiguous float32 HBM tensor [B, C, L]")
     b, c, length = x.shape
-    _check(_lib.rvc_rownorm_gelu_f32(x.data_ptr(), gamma.data_ptr() if gamma is not None else None,
-                                     beta.data_ptr() if beta is not None else None, x.data_ptr(), b, c, length, float(eps), _stream()),
-           "rvc_rownorm_gelu_f32")
+    _call("rvc_rownorm_gelu_f32", _device(x, gamma, beta), x.data_ptr(), _ptr(gamma), _ptr(beta), x.data_ptr(), b, c, length, float(eps))
     return x
 
 
 def gate_tanh_sigmoid(x: torch.Tensor) -> torch.Tensor:
     """x [B, 2H, T] -> tanh(x[:, :H]) * sigmoid(x[:, H:]) [B, H, T]"""
-    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3 and x.shape[1] % 2 == 0
+    if not (_is_f32_hbm(x) and x.dim() == 3 and x.shape[1] % 2 == 0):
+        raise NativeError("gate_tanh_sigmoid wants a contiguous float32 HBM tensor [B, 2H, T]")
     b, c2, t = x.shape
     out = torch.empty(b, c2 // 2, t, dtype=torch.float32, device=x.device)
-    _check(_lib.rvc_gate_tanh_sigmoid_f32(x.data_ptr(), out.data_ptr(), b, c2 // 2, t, _stream()), "rvc_gate_tanh_sigmoid_f32")
+    _call("rvc_gate_tanh_sigmoid_f32", x.device, x.data_ptr(), out.data_ptr(), b, c2 // 2, t)
     return out
 
 
@@ -670,7 +717,8 @@ class Comm:
     """RCCL communicator of the job (one rank per GPU), created collectively from rank 0's 128-byte id."""
 
     def __init__(self, unique_id: bytes, n_ranks: int, rank: int):
-        assert len(unique_id) == COMM_ID_BYTES
+        if len(unique_id) != COMM_ID_BYTES:
+            raise NativeError(f"Comm wants the {COMM_ID_BYTES}-byte id of comm_unique_id, got {len(unique_id)} bytes")
         self._h = c_void_p()
         _check(_lib.rvc_comm_create(ctypes.create_string_buffer(unique_id, COMM_ID_BYTES), int(n_ranks), int(rank),
                                     ctypes.byref(self._h)), "rvc_comm_create")
@@ -682,11 +730,10 @@ class Comm:
         return {"n_ranks": n.value, "rank": r.value, "rccl_version": v.value, "library": path.value.decode()}
 
     def broadcast_(self, t: torch.Tensor, root: int = 0) -> torch.Tensor:
-        """In-place broadcast of a contiguous HBM tensor's bytes from ``root`` on torch's current stream."""
+        """In-place broadcast of a contiguous HBM tensor's bytes from ``root`` on the current stream of the tensor's device."""
         if not t.is_cuda or not t.is_contiguous():
             raise NativeError("Comm.broadcast_ wants a contiguous HBM tensor")
-        _check(_lib.rvc_index_broadcast(self._h, t.data_ptr(), t.numel() * t.element_size(), int(root), _stream()),
-               "rvc_index_broadcast")
+        _call("rvc_index_broadcast", t.device, self._h, t.data_ptr(), t.numel() * t.element_size(), int(root))
         return t
 
     def destroy(self):
@@ -705,89 +752,100 @@ def checksum64(t: torch.Tensor) -> torch.Tensor:
     if not t.is_cuda or not t.is_contiguous():
         raise NativeError("checksum64 wants a contiguous HBM tensor")
     out = torch.empty(2, dtype=torch.int64, device=t.device)
-    _check(_lib.rvc_checksum64(t.data_ptr(), t.numel() * t.element_size(), out.data_ptr(), _stream()), "rvc_checksum64")
+    _call("rvc_checksum64", t.device, t.data_ptr(), t.numel() * t.element_size(), out.data_ptr())
     return out
 
 
-# ---- conv1d (unit-test entry) ----------------------------------------------------------------------
+# ---- conv1d: fp32 direct (unit-test entry), Winograd fp32 / bf16x3, and K3d / K3h, the square direct form (C = 128 / 256) of
+# ---- csrc/convbf1.hip on two operand formats -- one body, the entry point chosen by name ------------------------------------
 def conv1d_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    w = w.detach().float().cpu().contiguous()
+    w = _host(w)
     packed = torch.empty(w.numel(), dtype=torch.float32, device=device)
-    _check(_lib.rvc_conv1d_pack_weight(w.data_ptr(), w.shape[0], w.shape[1], w.shape[2], packed.data_ptr(), _stream()),
-           "rvc_conv1d_pack_weight")
+    _call("rvc_conv1d_pack_weight", packed.device, w.data_ptr(), w.shape[0], w.shape[1], w.shape[2], packed.data_ptr())
     return packed
 
 
-def conv1d_forward(x, w_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0):
-    return conv1d_forward_into(x, w_packed, bias, c_out, k, dilation, slope_in, res=res, acc=acc, out_scale=out_scale)
-
-
-def conv1d_forward_into(x, w_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    x = _dev_f32(x, "x")
-    b, c_in, length = x.shape
-    y = out if out is not None else torch.empty((b, c_out, length), dtype=torch.float32, device=x.device)
-    _check(_lib.rvc_conv1d_forward(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                   res.data_ptr() if res is not None else None,
-                                   acc.data_ptr() if acc is not None else None, y.data_ptr(), b, c_in, c_out, length, k,
-                                   dilation, float(slope_in), float(out_scale), _stream()), "rvc_conv1d_forward")
-    return y
-
-
 def conv1d_wino_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    w = w.detach().float().cpu().contiguous()
+    w = _host(w)
     c_out, c_in, k = w.shape
     u = torch.empty(3 * ((k + 2) // 3) * c_in * c_out, dtype=torch.float32, device=device)
-    _check(_lib.rvc_conv1d_wino_pack_weight(w.data_ptr(), c_out, c_in, k, u.data_ptr(), _stream()), "rvc_conv1d_wino_pack_weight")
+    _call("rvc_conv1d_wino_pack_weight", u.device, w.data_ptr(), c_out, c_in, k, u.data_ptr())
     return u
-
-
-def conv1d_wino_forward(x, u_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    x = _dev_f32(x, "x")
-    b, c_in, length = x.shape
-    y = out if out is not None else torch.empty((b, c_out, length), dtype=torch.float32, device=x.device)
-    _check(_lib.rvc_conv1d_wino_forward(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                        res.data_ptr() if res is not None else None,
-                                        acc.data_ptr() if acc is not None else None, y.data_ptr(), b, c_in, c_out, length, k,
-                                        dilation, float(slope_in), float(out_scale), _stream()), "rvc_conv1d_wino_forward")
-    return y
 
 
 def conv1d_winobf_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    w = w.detach().float().cpu().contiguous()
-    c_out, c_in, k = w.shape
-    n = c_size_t()
-    _check(_lib.rvc_conv1d_winobf_weight_bytes(c_out, c_in, k, ctypes.byref(n)), "rvc_conv1d_winobf_weight_bytes")
-    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_conv1d_winobf_pack_weight(w.data_ptr(), c_out, c_in, k, u.data_ptr(), _stream()), "rvc_conv1d_winobf_pack_weight")
-    return u
+    w = _host(w)
+    return _pack_slab("rvc_conv1d_winobf", device, (w,), tuple(w.shape))
+
+
+def _conv1d_square_pack(stem: str, w: torch.Tensor, device) -> torch.Tensor:
+    w = _host(w)
+    c, c_in, k = w.shape
+    if c != c_in:
+        raise NativeError(f"{stem[4:]}: a square conv expected, got {tuple(w.shape)}")
+    return _pack_slab(stem, device, (w,), (c, k))
+
+
+def conv1d_bf16w_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
+    """nn.Conv1d weight [c, c, k] -> one-term direct-form fragment slab on the device (the taps ROUNDED to bf16)."""
+    return _conv1d_square_pack("rvc_conv1d_bf16w", w, device)
+
+
+def conv1d_f16x2_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
+    """nn.Conv1d weight [c, c, k] -> fp16 (hi, lo * 2^11) direct-form fragment slab on the device; raises for a tap that is
+    non-finite or beyond +-65504."""
+    return _conv1d_square_pack("rvc_conv1d_f16x2", w, device)
+
+
+def _conv1d(name: str, x, w_packed, bias, c_out, k, dilation, slope_in, res, acc, out_scale, out):
+    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM through the entry point `name`.
+    c_out None: a square direct-form kernel, which takes one channel count and refuses y aliasing x."""
+    x = _dev_f32(x, "x")
+    b, c_in, length = x.shape
+    square = c_out is None
+    y = out if out is not None else torch.empty((b, c_in if square else c_out, length), dtype=torch.float32, device=x.device)
+    if square and y.data_ptr() == x.data_ptr():
+        raise NativeError(f"{name[4:-8]}: x and y must not alias")
+    _call(name, _device(x, w_packed, bias, res, acc, y), x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(res), _ptr(acc), y.data_ptr(),
+          b, *((c_in,) if square else (c_in, c_out)), length, k, dilation, float(slope_in), float(out_scale))
+    return y
+
+
+def conv1d_forward(x, w_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0):
+    return _conv1d("rvc_conv1d_forward", x, w_packed, bias, c_out, k, dilation, slope_in, res, acc, out_scale, None)
+
+
+def conv1d_forward_into(x, w_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
+    return _conv1d("rvc_conv1d_forward", x, w_packed, bias, c_out, k, dilation, slope_in, res, acc, out_scale, out)
+
+
+def conv1d_wino_forward(x, u_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
+    return _conv1d("rvc_conv1d_wino_forward", x, u_packed, bias, c_out, k, dilation, slope_in, res, acc, out_scale, out)
 
 
 def conv1d_winobf_forward(x, u_packed, bias, c_out, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    x = _dev_f32(x, "x")
-    b, c_in, length = x.shape
-    y = out if out is not None else torch.empty((b, c_out, length), dtype=torch.float32, device=x.device)
-    _check(_lib.rvc_conv1d_winobf_forward(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                          res.data_ptr() if res is not None else None,
-                                          acc.data_ptr() if acc is not None else None, y.data_ptr(), b, c_in, c_out, length, k,
-                                          dilation, float(slope_in), float(out_scale), _stream()), "rvc_conv1d_winobf_forward")
-    return y
+    return _conv1d("rvc_conv1d_winobf_forward", x, u_packed, bias, c_out, k, dilation, slope_in, res, acc, out_scale, out)
+
+
+def conv1d_bf16w_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
+    """C = 128 / 256 (K3d: the taps rounded to bf16)."""
+    return _conv1d("rvc_conv1d_bf16w_forward", x, u_packed, bias, None, k, dilation, slope_in, res, acc, out_scale, out)
+
+
+def conv1d_f16x2_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
+    """C = 128 / 256 (K3h: fp32 taps on error-corrected fp16 pairs)."""
+    return _conv1d("rvc_conv1d_f16x2_forward", x, u_packed, bias, None, k, dilation, slope_in, res, acc, out_scale, out)
 
 
 # ---- K3f: fused ResBlock pair (dilated conv -> conv + residual) on the bf16 matrix cores -------------------------
 def resblock_bf16x3_pack_weight(w1: torch.Tensor, w2: torch.Tensor, device, bf16_taps: bool = False) -> torch.Tensor:
     """The two nn.Conv1d weights [c, c, k] of one ResBlock dilation -> fragment slab on the device.  bf16_taps: the taps rounded to
     bf16 (BASELINE cfg 4's weight storage), one fragment per group instead of three -- for resblock_bf16x3_forward(bf16_taps=True)."""
-    w1 = w1.detach().float().cpu().contiguous()
-    w2 = w2.detach().float().cpu().contiguous()
+    w1, w2 = _host(w1), _host(w2)
     c, c_in, k = w1.shape
     if c != c_in or w2.shape != w1.shape:
         raise NativeError(f"resblock pair: square convs of one shape expected, got {tuple(w1.shape)} and {tuple(w2.shape)}")
-    stem = "rvc_resblock_bf16w" if bf16_taps else "rvc_resblock_bf16x3"
-    n = c_size_t()
-    _check(getattr(_lib, stem + "_weight_bytes")(c, k, ctypes.byref(n)), stem + "_weight_bytes")
-    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(getattr(_lib, stem + "_pack_weight")(w1.data_ptr(), w2.data_ptr(), c, k, u.data_ptr(), _stream()), stem + "_pack_weight")
-    return u
+    return _pack_slab("rvc_resblock_bf16w" if bf16_taps else "rvc_resblock_bf16x3", device, (w1, w2), (c, k))
 
 
 def resblock_bf16x3_forward(x, u_packed, b1, b2, k, dilation=1, slope=0.1, acc=None, out_scale=1.0, out=None, bf16_taps: bool = False):
@@ -798,78 +856,22 @@ def resblock_bf16x3_forward(x, u_packed, b1, b2, k, dilation=1, slope=0.1, acc=N
     y = out if out is not None else torch.empty_like(x)
     if y.data_ptr() == x.data_ptr():
         raise NativeError("resblock pair: x and y must not alias")
-    name = "rvc_resblock_bf16w_forward" if bf16_taps else "rvc_resblock_bf16x3_forward"
-    _check(getattr(_lib, name)(x.data_ptr(), u_packed.data_ptr(), b1.data_ptr() if b1 is not None else None,
-                               b2.data_ptr() if b2 is not None else None, acc.data_ptr() if acc is not None else None,
-                               y.data_ptr(), b, c, length, k, dilation, float(slope), float(out_scale), _stream()), name)
+    _call("rvc_resblock_bf16w_forward" if bf16_taps else "rvc_resblock_bf16x3_forward", _device(x, u_packed, b1, b2, acc, y),
+          x.data_ptr(), u_packed.data_ptr(), _ptr(b1), _ptr(b2), _ptr(acc), y.data_ptr(), b, c, length, k, dilation, float(slope),
+          float(out_scale))
     return y
-
-
-# ---- K3d / K3h: one square conv in direct form (C = 128 / 256), one kernel template (csrc/convbf1.hip) on two operand formats ---
-def _conv1d_direct_pack(stem: str, label: str, w: torch.Tensor, device) -> torch.Tensor:
-    """`stem`: the entry points' common prefix (rvc_conv1d_bf16w / rvc_conv1d_f16x2), `label`: what messages call the format."""
-    w = w.detach().float().cpu().contiguous()
-    c, c_in, k = w.shape
-    if c != c_in:
-        raise NativeError(f"{label}: a square conv expected, got {tuple(w.shape)}")
-    n = c_size_t()
-    _check(getattr(_lib, stem + "_weight_bytes")(c, k, ctypes.byref(n)), stem + "_weight_bytes")
-    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(getattr(_lib, stem + "_pack_weight")(w.data_ptr(), c, k, u.data_ptr(), _stream()), stem + "_pack_weight")
-    return u
-
-
-def _conv1d_direct_forward(stem: str, label: str, x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out):
-    x = _dev_f32(x, "x")
-    b, c, length = x.shape
-    y = out if out is not None else torch.empty_like(x)
-    if y.data_ptr() == x.data_ptr():
-        raise NativeError(f"{label}: x and y must not alias")
-    _check(getattr(_lib, stem + "_forward")(x.data_ptr(), u_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                            res.data_ptr() if res is not None else None, acc.data_ptr() if acc is not None else None,
-                                            y.data_ptr(), b, c, length, k, dilation, float(slope_in), float(out_scale), _stream()),
-           stem + "_forward")
-    return y
-
-
-def conv1d_bf16w_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    """nn.Conv1d weight [c, c, k] -> one-term direct-form fragment slab on the device (the taps ROUNDED to bf16)."""
-    return _conv1d_direct_pack("rvc_conv1d_bf16w", "conv1d_bf16w", w, device)
-
-
-def conv1d_bf16w_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3d)."""
-    return _conv1d_direct_forward("rvc_conv1d_bf16w", "conv1d_bf16w", x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out)
-
-
-def conv1d_f16x2_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
-    """nn.Conv1d weight [c, c, k] -> fp16 (hi, lo * 2^11) direct-form fragment slab on the device; raises for a tap that is
-    non-finite or beyond +-65504."""
-    return _conv1d_direct_pack("rvc_conv1d_f16x2", "conv1d_f16x2", w, device)
-
-
-def conv1d_f16x2_forward(x, u_packed, bias, k, dilation=1, slope_in=1.0, res=None, acc=None, out_scale=1.0, out=None):
-    """y = out_scale * (conv_d(leaky(x, slope_in)) + bias [+ res] [+ acc]) for x [B, C, L] in HBM, C = 128 / 256 (K3h: fp32 taps on
-    error-corrected fp16 pairs)."""
-    return _conv1d_direct_forward("rvc_conv1d_f16x2", "conv1d_f16x2", x, u_packed, bias, k, dilation, slope_in, res, acc, out_scale, out)
 
 
 # ---- K3u: upsampling step (polyphase ConvTranspose1d + folded noise conv) on the bf16 matrix cores -----------------
 def upsample_bf16x3_pack_weight(up_w: torch.Tensor, noise_w, bias, rate: int, nc_stride: int, device):
     """ConvTranspose1d weight [c_in, c_out, ksize] (+ the noise conv's weight [c_out, 1, nc_k] or None, + the summed bias [c_out] or None)
     -> (fragment slab, noise weights [c_out, nc_k] or None, bias or None) on the device, the triple `upsample_bf16x3_forward` takes."""
-    up_w = up_w.detach().float().cpu().contiguous()
+    up_w = _host(up_w)
     c_in, c_out, ksize = up_w.shape
-    nc_k, nw = 0, None
-    if noise_w is not None:
-        nw = noise_w.detach().float().cpu().reshape(c_out, -1).contiguous()
-        nc_k = nw.shape[1]
-    b = bias.detach().float().cpu().contiguous() if bias is not None else None
-    n = c_size_t()
-    _check(_lib.rvc_upsample_bf16x3_weight_bytes(c_in, c_out, rate, ksize, nc_k, nc_stride, ctypes.byref(n)), "rvc_upsample_bf16x3_weight_bytes")
-    u = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_upsample_bf16x3_pack_weight(up_w.data_ptr(), nw.data_ptr() if nw is not None else None, b.data_ptr() if b is not None else None,
-                                                c_in, c_out, rate, ksize, nc_k, nc_stride, u.data_ptr(), _stream()), "rvc_upsample_bf16x3_pack_weight")
+    nw = _host(noise_w).reshape(c_out, -1).contiguous() if noise_w is not None else None
+    nc_k = nw.shape[1] if nw is not None else 0
+    b = _host(bias) if bias is not None else None
+    u = _pack_slab("rvc_upsample_bf16x3", device, (up_w, nw, b), (c_in, c_out, rate, ksize, nc_k, nc_stride))
     return u, (nw.to(device) if nw is not None else None), (b.to(device) if b is not None else None)
 
 
@@ -882,10 +884,9 @@ def upsample_bf16x3_forward(x, har, packed, c_out, rate, ksize, pad, nc_stride=1
     y = torch.empty((b, c_out, l_out), dtype=torch.float32, device=x.device)
     if har is not None:
         har = _dev_f32(har, "har")
-    _check(_lib.rvc_upsample_bf16x3_forward(x.data_ptr(), har.data_ptr() if har is not None else None, har.shape[-1] if har is not None else 0,
-                                            u.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                            y.data_ptr(), b, c_in, c_out, length, rate, ksize, pad, nw.shape[1] if nw is not None else 0, nc_stride,
-                                            nc_pad, float(slope), _stream()), "rvc_upsample_bf16x3_forward")
+    _call("rvc_upsample_bf16x3_forward", _device(x, har, u, bias), x.data_ptr(), _ptr(har), har.shape[-1] if har is not None else 0,
+          u.data_ptr(), _ptr(bias), y.data_ptr(), b, c_in, c_out, length, rate, ksize, pad, nw.shape[1] if nw is not None else 0,
+          nc_stride, nc_pad, float(slope))
     return y
 
 
@@ -897,14 +898,10 @@ def resblock_bf16x3_set_enabled(enabled: bool) -> None:
 # ---- K11: fp32 GEMM / strided conv1d as exact bf16x3 splits on the bf16 matrix cores ----------------------------
 def gemm_bf16x3_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
     """nn.Linear weight [out, in] or nn.Conv1d weight [c_out, c_in, taps] -> fragment slab on the device."""
-    w = w.detach().float().cpu().contiguous()
+    w = _host(w)
     taps = w.shape[2] if w.dim() == 3 else 1
     m, k_total = w.shape[0], w.shape[1] * taps
-    n = c_size_t()
-    _check(_lib.rvc_gemm_bf16x3_weight_bytes(m, k_total, ctypes.byref(n)), "rvc_gemm_bf16x3_weight_bytes")
-    a = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_gemm_bf16x3_pack_weight(w.data_ptr(), m, k_total, taps, a.data_ptr(), _stream()), "rvc_gemm_bf16x3_pack_weight")
-    return a
+    return _pack_slab("rvc_gemm_bf16x3", device, (w,), (m, k_total), (m, k_total, taps))
 
 
 def linear_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, out_features: int, act: str = "none", res=None) -> torch.Tensor:
@@ -915,10 +912,10 @@ def linear_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, out_features: i
     y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32, device=x.device)
     if res is not None:
         res = _dev_f32(res, "res")
-        assert res.shape == y.shape
-    _check(_lib.rvc_linear_bf16x3(x.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                  res.data_ptr() if res is not None else None, y.data_ptr(), n_rows, in_features, out_features,
-                                  {"none": 0, "gelu": 1}[act], _stream()), "rvc_linear_bf16x3")
+        if res.shape != y.shape:
+            raise NativeError(f"linear_bf16x3: res {tuple(res.shape)} must have the result's shape {tuple(y.shape)}")
+    _call("rvc_linear_bf16x3", _device(x, a_packed, bias, res), x.data_ptr(), a_packed.data_ptr(), _ptr(bias), _ptr(res), y.data_ptr(),
+          n_rows, in_features, out_features, {"none": 0, "gelu": 1}[act])
     return y
 
 
@@ -928,18 +925,17 @@ def glu_dwconv_silu(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor) -> tor
     x, w, bias = _dev_f32(x, "x"), _dev_f32(w, "w"), _dev_f32(bias, "bias")
     n_rows, c = x.shape[0], x.shape[1] // 2
     y = torch.empty((n_rows, c), dtype=torch.float32, device=x.device)
-    _check(_lib.rvc_glu_dwconv_silu_f32(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), n_rows, c, w.shape[1], _stream()),
-           "rvc_glu_dwconv_silu_f32")
+    _call("rvc_glu_dwconv_silu_f32", _device(x, w, bias), x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), n_rows, c, w.shape[1])
     return y
 
 
 def layernorm_rows(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """nn.LayerNorm over the last axis of x [..., F] (F a multiple of 64, <= 1024)."""
-    x = _dev_f32(x, "x")
+    x, gamma, beta = _dev_f32(x, "x"), _dev_f32(gamma, "gamma"), _dev_f32(beta, "beta")
     f = x.shape[-1]
     y = torch.empty_like(x)
-    _check(_lib.rvc_layernorm_rows_f32(x.data_ptr(), _dev_f32(gamma, "gamma").data_ptr(), _dev_f32(beta, "beta").data_ptr(), float(eps),
-                                       y.data_ptr(), x.numel() // f, f, _stream()), "rvc_layernorm_rows_f32")
+    _call("rvc_layernorm_rows_f32", _device(x, gamma, beta), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), y.data_ptr(),
+          x.numel() // f, f)
     return y
 
 
@@ -948,13 +944,11 @@ def groupnorm_lrelu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gr
     """leaky_relu(nn.GroupNorm(groups, C)(x), slope) for channel-major x [C, L]."""
     x = _dev_f32(x, "x")
     c, length = x.shape
-    need = c_size_t()
-    _check(_lib.rvc_groupnorm_workspace_bytes(c, length, groups, ctypes.byref(need)), "rvc_groupnorm_workspace_bytes")
-    ws = _ws.get("groupnorm", need.value, x.device)
+    ws = _workspace("groupnorm", x.device, "rvc_groupnorm_workspace_bytes", c, length, groups)
     y = torch.empty_like(x)
-    _check(_lib.rvc_groupnorm_lrelu_f32(x.data_ptr(), _dev_f32(gamma, "gamma").data_ptr(), _dev_f32(beta, "beta").data_ptr(), groups,
-                                        float(eps), float(slope), y.data_ptr(), c, length, ws.data_ptr(), ws.numel(), _stream()),
-           "rvc_groupnorm_lrelu_f32")
+    gamma, beta = _dev_f32(gamma, "gamma"), _dev_f32(beta, "beta")
+    _call("rvc_groupnorm_lrelu_f32", _device(x, gamma, beta), x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), groups, float(eps),
+          float(slope), y.data_ptr(), c, length, ws.data_ptr(), ws.numel())
     return y
 
 
@@ -965,11 +959,11 @@ def fcpe_decode(logits: torch.Tensor, cent_table: torch.Tensor, out_dims: int, t
     n_rows, ld = logits.shape
     if cent_table.numel() != out_dims:
         raise NativeError(f"cent_table has {cent_table.numel()} entries, out_dims is {out_dims}")
-    f0 = torch.empty(n_rows, dtype=torch.float32, device=logits.device)
-    latent = torch.empty((n_rows, out_dims), dtype=torch.float32, device=logits.device) if want_latent else None
-    _check(_lib.rvc_fcpe_decode_f32(logits.data_ptr(), cent_table.data_ptr(), out_dims, ld, float(threshold), float(f0_min),
-                                    f0.data_ptr(), latent.data_ptr() if latent is not None else None, n_rows, _stream()),
-           "rvc_fcpe_decode_f32")
+    dev = _device(logits, cent_table)
+    f0 = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    latent = torch.empty((n_rows, out_dims), dtype=torch.float32, device=dev) if want_latent else None
+    _call("rvc_fcpe_decode_f32", dev, logits.data_ptr(), cent_table.data_ptr(), out_dims, ld, float(threshold), float(f0_min),
+          f0.data_ptr(), _ptr(latent), n_rows)
     return f0, latent
 
 
@@ -988,7 +982,7 @@ def split_rows_bf16x3(x: torch.Tensor, out: torch.Tensor | None = None) -> torch
     x = _dev_f32(x, "x")
     n_rows, k = x.shape
     xs = out if out is not None else planes_empty(n_rows, k, x.device)
-    _check(_lib.rvc_split_rows_bf16x3(x.data_ptr(), xs.data_ptr(), n_rows, xs.shape[1], k, _stream()), "rvc_split_rows_bf16x3")
+    _call("rvc_split_rows_bf16x3", _device(x, xs), x.data_ptr(), xs.data_ptr(), n_rows, xs.shape[1], k)
     return xs
 
 
@@ -1005,22 +999,15 @@ def linear_bf16x3_presplit(xs: torch.Tensor, a_packed: torch.Tensor, bias, n_row
         y = out if out is not None else torch.empty((3, n_pad, out_features), dtype=torch.bfloat16, device=xs.device)
     else:
         y = out if out is not None else torch.empty((k_parts, n_rows, out_features), dtype=torch.float32, device=xs.device)
-    _check(_lib.rvc_linear_bf16x3_presplit(xs.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                           y.data_ptr() if m != 1 else None, y.data_ptr() if m == 1 else None, n_rows, n_pad,
-                                           in_features, out_features, m, k_parts, _stream()), "rvc_linear_bf16x3_presplit")
+    _call("rvc_linear_bf16x3_presplit", _device(xs, a_packed, bias, y), xs.data_ptr(), a_packed.data_ptr(), _ptr(bias),
+          y.data_ptr() if m != 1 else None, y.data_ptr() if m == 1 else None, n_rows, n_pad, in_features, out_features, m, k_parts)
     return y
 
 
 def posconv_bf16x3_pack_weight(w: torch.Tensor, groups: int, device) -> torch.Tensor:
     """conv.weight [D, D / groups, taps] (weight norm folded) -> K14's fragment slab in HBM."""
-    w = w.detach().float().cpu().contiguous()
-    d, cg, taps = w.shape
-    need = c_size_t()
-    _check(_lib.rvc_posconv_bf16x3_weight_bytes(d, groups, taps, ctypes.byref(need)), "rvc_posconv_bf16x3_weight_bytes")
-    a = torch.empty(need.value // 2, dtype=torch.int16, device=device)
-    with torch.cuda.device(a.device):
-        _check(_lib.rvc_posconv_bf16x3_pack_weight(w.data_ptr(), d, groups, taps, a.data_ptr(), _stream()), "rvc_posconv_bf16x3_pack_weight")
-    return a
+    w = _host(w)
+    return _pack_slab("rvc_posconv_bf16x3", device, (w,), (w.shape[0], groups, w.shape[2]))
 
 
 def posconv_gelu_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, groups: int, taps: int, padding: int) -> torch.Tensor:
@@ -1028,8 +1015,8 @@ def posconv_gelu_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, groups: i
     x = _dev_f32(x, "x")
     t, d = x.shape
     y = torch.empty_like(x)
-    _check(_lib.rvc_posconv_gelu_bf16x3(x.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                        t, d, groups, taps, padding, _stream()), "rvc_posconv_gelu_bf16x3")
+    _call("rvc_posconv_gelu_bf16x3", _device(x, a_packed, bias), x.data_ptr(), a_packed.data_ptr(), _ptr(bias), y.data_ptr(), t, d, groups,
+          taps, padding)
     return y
 
 
@@ -1038,17 +1025,14 @@ def hubert_conv0_frames_bf16x3(wav: torch.Tensor, w: torch.Tensor, gamma, beta, 
     (time-major planes [3, frames_padded, C], frames)."""
     wav = _dev_f32(wav, "wav")
     w2 = _dev_f32(w.reshape(w.shape[0], -1), "w")
+    dev = _device(wav, w2, gamma, beta)
     c, taps = w2.shape
     n = wav.numel()
     frames = (n - taps) // stride + 1
-    ys = planes_empty(frames, c, wav.device)
-    need = c_size_t()
-    _check(_lib.rvc_hubert_conv0_workspace_bytes(c, ctypes.byref(need)), "rvc_hubert_conv0_workspace_bytes")
-    ws = _ws.get("hubert_conv0", need.value, wav.device)
-    _check(_lib.rvc_hubert_conv0_frames_bf16x3(wav.data_ptr(), n, w2.data_ptr(), c, taps, stride,
-                                               gamma.data_ptr() if gamma is not None else None,
-                                               beta.data_ptr() if beta is not None else None, float(eps), ws.data_ptr(), ws.numel(),
-                                               ys.data_ptr(), ys.shape[1], _stream()), "rvc_hubert_conv0_frames_bf16x3")
+    ys = planes_empty(frames, c, dev)
+    ws = _workspace("hubert_conv0", dev, "rvc_hubert_conv0_workspace_bytes", c)
+    _call("rvc_hubert_conv0_frames_bf16x3", dev, wav.data_ptr(), n, w2.data_ptr(), c, taps, stride, _ptr(gamma), _ptr(beta), float(eps),
+          ws.data_ptr(), ws.numel(), ys.data_ptr(), ys.shape[1])
     return ys, frames
 
 
@@ -1063,10 +1047,8 @@ def conv1d_frames_bf16x3(xs: torch.Tensor, n_frames_in: int, a_packed: torch.Ten
     if frames <= 0:
         raise NativeError("conv1d_frames_bf16x3: the input is shorter than one window")
     y = planes_empty(frames, out_channels, xs.device) if m == 1 else torch.empty((frames, out_channels), dtype=torch.float32, device=xs.device)
-    _check(_lib.rvc_conv1d_frames_bf16x3(xs.data_ptr(), n_frames_in, n_pad_in, c, taps, stride, a_packed.data_ptr(),
-                                         bias.data_ptr() if bias is not None else None, y.data_ptr() if m != 1 else None,
-                                         y.data_ptr() if m == 1 else None, rows_padded(frames), out_channels, m, _stream()),
-           "rvc_conv1d_frames_bf16x3")
+    _call("rvc_conv1d_frames_bf16x3", _device(xs, a_packed, bias), xs.data_ptr(), n_frames_in, n_pad_in, c, taps, stride, a_packed.data_ptr(),
+          _ptr(bias), y.data_ptr() if m != 1 else None, y.data_ptr() if m == 1 else None, rows_padded(frames), out_channels, m)
     return y, frames
 
 
@@ -1077,12 +1059,8 @@ def bias_residual_layernorm_bf16x3(parts: torch.Tensor, bias, res, gamma, beta, 
     y = y if y is not None else torch.empty((n_rows, m), dtype=torch.float32, device=parts.device)
     if want_planes and ys is None:
         ys = planes_empty(n_rows, m, parts.device)
-    _check(_lib.rvc_bias_residual_layernorm_bf16x3(parts.data_ptr(), n_parts, bias.data_ptr() if bias is not None else None,
-                                                   res.data_ptr() if res is not None else None,
-                                                   gamma.data_ptr() if gamma is not None else None,
-                                                   beta.data_ptr() if beta is not None else None, float(eps), y.data_ptr(),
-                                                   ys.data_ptr() if ys is not None else None, n_rows, ys.shape[1] if ys is not None else n_rows,
-                                                   m, _stream()), "rvc_bias_residual_layernorm_bf16x3")
+    _call("rvc_bias_residual_layernorm_bf16x3", _device(parts, bias, res, gamma, beta, y, ys), parts.data_ptr(), n_parts, _ptr(bias),
+          _ptr(res), _ptr(gamma), _ptr(beta), float(eps), y.data_ptr(), _ptr(ys), n_rows, ys.shape[1] if ys is not None else n_rows, m)
     return y, ys
 
 
@@ -1095,20 +1073,18 @@ def conv1d_bf16x3(x: torch.Tensor, a_packed: torch.Tensor, bias, c_out: int, k: 
     y = torch.empty((b, c_out, l_out), dtype=torch.float32, device=x.device)
     if y.numel() == 0:   # an input shorter than one window: an empty result, and no call with an empty tensor's NULL pointer
         return y
-    _check(_lib.rvc_conv1d_bf16x3(x.data_ptr(), a_packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), b,
-                                  c_in, c_out, l_in, k, stride, padding, {"none": 0, "gelu": 1}[act], _stream()), "rvc_conv1d_bf16x3")
+    _call("rvc_conv1d_bf16x3", _device(x, a_packed, bias), x.data_ptr(), a_packed.data_ptr(), _ptr(bias), y.data_ptr(), b, c_in, c_out, l_in,
+          k, stride, padding, {"none": 0, "gelu": 1}[act])
     return y
 
 
-# ---- K10: conv2d 3x3 / 1x1 of the RMVPE U-Net -------------------------------------------------------------
+# ---- K10 / K10b: conv2d 3x3 / 1x1 of the RMVPE U-Net, in fp32 and as exact bf16x3 products on the bf16 matrix cores ----------
 def conv2d_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
     """torch conv2d weight [C_out, C_in, kh, kw] (3x3 or 1x1) -> packed taps in HBM."""
-    w = w.detach().float().cpu().contiguous()
-    c_out, c_in, kh, kw = w.shape
-    n = c_size_t()
-    _check(_lib.rvc_conv2d_packed_floats(c_out, c_in, kh, kw, ctypes.byref(n)), "rvc_conv2d_packed_floats")
-    out = torch.empty(n.value, dtype=torch.float32, device=device)
-    _check(_lib.rvc_conv2d_pack_weight(w.data_ptr(), c_out, c_in, kh, kw, out.data_ptr(), _stream()), "rvc_conv2d_pack_weight")
+    w = _host(w)
+    device = _cuda_device(device)
+    out = torch.empty(_size("rvc_conv2d_packed_floats", device, *w.shape), dtype=torch.float32, device=device)
+    _call("rvc_conv2d_pack_weight", device, w.data_ptr(), *w.shape, out.data_ptr())
     return out
 
 
@@ -1116,22 +1092,6 @@ def conv2d_supported(c_in: int, width: int) -> bool:
     return c_in % 8 == 0 and 4 <= width <= 128 and width & (width - 1) == 0
 
 
-def conv2d_forward(x, w_packed, bias, c_out, ksize=3, relu=False, res=None, out=None):
-    """y = act(conv2d(x, w, padding=ksize // 2) + bias) + res  (x [B, C_in, H, W] float32 on the device)."""
-    x = _dev_f32(x, "x")
-    b, c_in, h, wd = x.shape
-    y = out if out is not None else torch.empty((b, c_out, h, wd), dtype=torch.float32, device=x.device)
-    need = c_size_t()
-    _check(_lib.rvc_conv2d_workspace_bytes(b, c_in, c_out, h, wd, ksize, ksize, ctypes.byref(need)), "rvc_conv2d_workspace_bytes")
-    ws = _ws.get("conv2d", need.value, x.device) if need.value else None
-    _check(_lib.rvc_conv2d_forward(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                   res.data_ptr() if res is not None else None, y.data_ptr(), b, c_in, c_out, h, wd, ksize, ksize,
-                                   1 if relu else 0, ws.data_ptr() if ws is not None else None, need.value, _stream()),
-           "rvc_conv2d_forward")
-    return y
-
-
-# ---- K10b: the same 3x3 conv as exact bf16x3 products on the bf16 matrix cores ------------------------------
 def conv2d_bf16x3_supported(c_in: int, c_out: int, height: int, width: int) -> bool:
     return bool(_lib.rvc_conv2d_bf16x3_supported(c_in, c_out, height, width))
 
@@ -1143,28 +1103,32 @@ def conv2d_bf16x3_packable(c_in: int, c_out: int) -> bool:
 
 def conv2d_bf16x3_pack_weight(w: torch.Tensor, device) -> torch.Tensor:
     """torch conv2d weight [C_out, C_in, 3, 3] -> bf16x3 tap fragments in HBM (int16 words)."""
-    w = w.detach().float().cpu().contiguous()
-    c_out, c_in, kh, kw = w.shape
-    n = c_size_t()
-    _check(_lib.rvc_conv2d_bf16x3_weight_bytes(c_out, c_in, kh, kw, ctypes.byref(n)), "rvc_conv2d_bf16x3_weight_bytes")
-    out = torch.empty(n.value // 2, dtype=torch.int16, device=device)
-    _check(_lib.rvc_conv2d_bf16x3_pack_weight(w.data_ptr(), c_out, c_in, kh, kw, out.data_ptr(), _stream()), "rvc_conv2d_bf16x3_pack_weight")
-    return out
+    w = _host(w)
+    return _pack_slab("rvc_conv2d_bf16x3", device, (w,), tuple(w.shape))
+
+
+def _conv2d(stem: str, x, w_packed, bias, c_out, taps: tuple, relu, res, out):
+    """<stem>_forward with the scratch <stem>_workspace_bytes asks for (none at all for most shapes); taps: (kh, kw), or () for the
+    entry point that is 3x3 only."""
+    x = _dev_f32(x, "x")
+    b, c_in, h, wd = x.shape
+    y = out if out is not None else torch.empty((b, c_out, h, wd), dtype=torch.float32, device=x.device)
+    dev = _device(x, w_packed, bias, res, y)
+    need = _size(stem + "_workspace_bytes", dev, b, c_in, c_out, h, wd, *taps)
+    ws = _ws.get("conv2d", need, dev) if need else None
+    _call(stem + "_forward", dev, x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(res), y.data_ptr(), b, c_in, c_out, h, wd, *taps,
+          1 if relu else 0, _ptr(ws), need)
+    return y
+
+
+def conv2d_forward(x, w_packed, bias, c_out, ksize=3, relu=False, res=None, out=None):
+    """y = act(conv2d(x, w, padding=ksize // 2) + bias) + res  (x [B, C_in, H, W] float32 on the device)."""
+    return _conv2d("rvc_conv2d", x, w_packed, bias, c_out, (ksize, ksize), relu, res, out)
 
 
 def conv2d_bf16x3_forward(x, u, bias, c_out, relu=False, res=None, out=None):
     """y = act(conv2d(x, w, padding=1) + bias) + res  (x [B, C_in, H, W] float32 on the device; u from conv2d_bf16x3_pack_weight)."""
-    x = _dev_f32(x, "x")
-    b, c_in, h, wd = x.shape
-    y = out if out is not None else torch.empty((b, c_out, h, wd), dtype=torch.float32, device=x.device)
-    need = c_size_t()
-    _check(_lib.rvc_conv2d_bf16x3_workspace_bytes(b, c_in, c_out, h, wd, ctypes.byref(need)), "rvc_conv2d_bf16x3_workspace_bytes")
-    ws = _ws.get("conv2d", need.value, x.device) if need.value else None
-    _check(_lib.rvc_conv2d_bf16x3_forward(x.data_ptr(), u.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                          res.data_ptr() if res is not None else None, y.data_ptr(), b, c_in, c_out, h, wd,
-                                          1 if relu else 0, ws.data_ptr() if ws is not None else None, need.value, _stream()),
-           "rvc_conv2d_bf16x3_forward")
-    return y
+    return _conv2d("rvc_conv2d_bf16x3", x, u, bias, c_out, (), relu, res, out)
 
 
 # ---- K2/K3 -----------------------------------------------------------------------------------------
@@ -1195,24 +1159,28 @@ def _decoder_config(vocoder, sr, *, in_channels=192, upsample_initial_channel=51
     return cfg
 
 
-def decoder_window_margin(vocoder: str, sr: int = 48000, **config) -> int:
-    """rvc_decoder_window_margin for a vocoder configuration (Decoder's keyword arguments): input frames on each side that an
-    output frame depends on; -1 for RefineGAN (not covered).  A host computation: needs no device."""
-    cfg = _decoder_config(vocoder, sr, **config)
+def _window_margin(cfg: DecoderConfig) -> int:
     frames = c_int()
     _check(_lib.rvc_decoder_window_margin(ctypes.byref(cfg), ctypes.byref(frames)), "rvc_decoder_window_margin")
     return frames.value
 
 
+def decoder_window_margin(vocoder: str, sr: int = 48000, **config) -> int:
+    """rvc_decoder_window_margin for a vocoder configuration (Decoder's keyword arguments): input frames on each side that an
+    output frame depends on; -1 for RefineGAN (not covered).  A host computation: needs no device."""
+    return _window_margin(_decoder_config(vocoder, sr, **config))
+
+
 class Decoder:
-    """Handle on the library's vocoder: weights are repacked into HBM once, forward() launches the chain."""
+    """Handle on the library's vocoder: weights are repacked into one device's HBM once, forward() launches the chain there."""
 
     def __init__(self, vocoder: str, sr: int, folded_weights: dict, *, in_channels=192, upsample_initial_channel=512,
                  gin_channels=256, upsample_rates=(12, 10, 2, 2), upsample_kernel_sizes=(24, 20, 4, 4),
                  res_kernel_sizes=(3, 7, 11), res_dilations=(1, 3, 5), weight_storage: str = "f32",
-                 arithmetic: str = "exact"):
+                 arithmetic: str = "exact", device=None):
         """arithmetic: "exact" (default), or "fp16x2" -- the square 128- / 256-channel ResBlock convs on error-corrected fp16
-        pairs (K3h): the fp32 result to ~2^-22 per product, faster; not with weight_storage="bf16"."""
+        pairs (K3h): the fp32 result to ~2^-22 per product, faster; not with weight_storage="bf16".
+        device: where the weights live and forward() runs (None: the current device)."""
         if not torch.cuda.is_available():
             raise NativeError("rvc_amd.Decoder needs a HIP device (no CPU fallback)")
         if arithmetic not in DEC_ARITHMETIC:
@@ -1221,6 +1189,7 @@ class Decoder:
                                           gin_channels=gin_channels, upsample_rates=upsample_rates,
                                           upsample_kernel_sizes=upsample_kernel_sizes, res_kernel_sizes=res_kernel_sizes,
                                           res_dilations=res_dilations, weight_storage=weight_storage)
+        self.device = _cuda_device(device)
         self._h = c_void_p()
         self.vocoder = vocoder
         _check(_lib.rvc_decoder_create(ctypes.byref(cfg), ctypes.byref(self._h)), "rvc_decoder_create")
@@ -1228,11 +1197,12 @@ class Decoder:
         if arithmetic != "exact":   # (the default handle makes exactly the calls it always made)
             _check(_lib.rvc_decoder_set_arithmetic(self._h, DEC_ARITHMETIC[arithmetic]), "rvc_decoder_set_arithmetic")
         for name, t in folded_weights.items():
-            t = t.detach().float().cpu().contiguous()
+            t = _host(t)
             shape = (c_int64 * t.dim())(*t.shape)
             _check(_lib.rvc_decoder_set_tensor(self._h, name.encode(), t.data_ptr(), shape, t.dim()),
                    f"rvc_decoder_set_tensor({name})")
-        _check(_lib.rvc_decoder_finalize(self._h), "rvc_decoder_finalize")
+        with torch.cuda.device(self.device):   # rvc_decoder_finalize allocates and uploads, and takes no stream
+            _check(_lib.rvc_decoder_finalize(self._h), "rvc_decoder_finalize")
         self.upp = _lib.rvc_decoder_upp(self._h)
 
     def __del__(self):
@@ -1250,42 +1220,33 @@ class Decoder:
         _check(_lib.rvc_decoder_set_branch_parallel(self._h, int(side_streams)), "rvc_decoder_set_branch_parallel")
 
     def set_tap(self, stage: int, tap: torch.Tensor | None):
-        _check(_lib.rvc_decoder_set_tap(self._h, stage, tap.data_ptr() if tap is not None else None),
-               "rvc_decoder_set_tap")
+        _check(_lib.rvc_decoder_set_tap(self._h, stage, _ptr(tap)), "rvc_decoder_set_tap")
 
     def window_margin(self) -> int:
         """Input frames on each side that an output frame depends on (rvc_decoder_window_margin); -1: RefineGAN, not covered."""
-        frames = c_int()
-        _check(_lib.rvc_decoder_window_margin(ctypes.byref(self._cfg), ctypes.byref(frames)), "rvc_decoder_window_margin")
-        return frames.value
+        return _window_margin(self._cfg)
 
     def forward(self, z: torch.Tensor, f0: torch.Tensor, g: torch.Tensor, *, src_randn: torch.Tensor,
                 src_rand: torch.Tensor | None = None, adain_randn: torch.Tensor | None = None,
                 keep: tuple | None = None) -> torch.Tensor:
         """keep = (lo, hi) in frames: only the samples [lo * upp, hi * upp) of the waveform, from the same full-length inputs
         (rvc_decoder_forward_window: the conv stack runs over those frames plus window_margin() on each side)."""
-        z, f0, g = _dev_f32(z, "z"), _dev_f32(f0, "f0"), _dev_f32(g, "g")
+        z, f0, g, src_randn = _dev_f32(z, "z"), _dev_f32(f0, "f0"), _dev_f32(g, "g"), _dev_f32(src_randn, "src_randn")
+        src_rand = _dev_f32(src_rand, "src_rand") if src_rand is not None else None
+        adain_randn = _dev_f32(adain_randn, "adain_randn") if adain_randn is not None else None
+        dev = self.device
+        if _device(z, f0, g, src_randn, src_rand, adain_randn) != dev:
+            raise NativeError(f"Decoder of {dev} got tensors on {z.device}")
         b, _, t = z.shape
-        noise = DecoderNoise()
-        src_randn = _dev_f32(src_randn, "src_randn")
-        noise.src_randn_dev = src_randn.data_ptr()
-        if src_rand is not None:
-            src_rand = _dev_f32(src_rand, "src_rand")
-            noise.src_rand_dev = src_rand.data_ptr()
-        if adain_randn is not None:
-            adain_randn = _dev_f32(adain_randn, "adain_randn")
-            noise.adain_randn_dev = adain_randn.data_ptr()
-        need = c_size_t()
-        _check(_lib.rvc_decoder_workspace_bytes(self._h, b, t, ctypes.byref(need)), "rvc_decoder_workspace_bytes")
-        ws = _ws.get("decoder", need.value, z.device)
+        noise = DecoderNoise(_ptr(src_rand), src_randn.data_ptr(), _ptr(adain_randn))
+        ws = _workspace("decoder", dev, "rvc_decoder_workspace_bytes", self._h, b, t)
         if keep is not None:
             lo, hi = int(keep[0]), int(keep[1])
-            out = torch.empty((b, 1, max(hi - lo, 0) * self.upp), dtype=torch.float32, device=z.device)
-            _check(_lib.rvc_decoder_forward_window(self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
-                                                   lo, hi, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "rvc_decoder_forward_window")
+            out = torch.empty((b, 1, max(hi - lo, 0) * self.upp), dtype=torch.float32, device=dev)
+            _call("rvc_decoder_forward_window", dev, self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
+                  lo, hi, out.data_ptr(), ws.data_ptr(), ws.numel())
             return out
-        out = torch.empty((b, 1, t * self.upp), dtype=torch.float32, device=z.device)
-        _check(_lib.rvc_decoder_forward(self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
-                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "rvc_decoder_forward")
+        out = torch.empty((b, 1, t * self.upp), dtype=torch.float32, device=dev)
+        _call("rvc_decoder_forward", dev, self._h, z.data_ptr(), f0.data_ptr(), g.data_ptr(), ctypes.byref(noise), b, t,
+              out.data_ptr(), ws.data_ptr(), ws.numel())
         return out

@@ -75,14 +75,13 @@ class Synthesizer:
         prepare_flow_weights(self.w)
         torch.cuda.synchronize(self.device)   # visible to every stream that will use them
         if self._dec_weights is not None and self.dec is None:
-            with torch.cuda.device(self.device):
-                self.dec = _native.Decoder(self.vocoder, self.sr, self._dec_weights, in_channels=self.inter_channels,
-                                           upsample_initial_channel=self.upsample_initial_channel,
-                                           gin_channels=self.gin_channels, upsample_rates=self.upsample_rates,
-                                           upsample_kernel_sizes=self.upsample_kernel_sizes,
-                                           res_kernel_sizes=self.resblock_kernel_sizes,
-                                           res_dilations=self.resblock_dilations, weight_storage=self.dec_weight_dtype,
-                                           arithmetic=self.dec_arithmetic)
+            self.dec = _native.Decoder(self.vocoder, self.sr, self._dec_weights, in_channels=self.inter_channels,
+                                       upsample_initial_channel=self.upsample_initial_channel,
+                                       gin_channels=self.gin_channels, upsample_rates=self.upsample_rates,
+                                       upsample_kernel_sizes=self.upsample_kernel_sizes,
+                                       res_kernel_sizes=self.resblock_kernel_sizes,
+                                       res_dilations=self.resblock_dilations, weight_storage=self.dec_weight_dtype,
+                                       arithmetic=self.dec_arithmetic, device=self.device)
 
     def to(self, device):
         device = torch.device(device)

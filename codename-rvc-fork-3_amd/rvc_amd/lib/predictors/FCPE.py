@@ -141,7 +141,8 @@ class FCPE:
         fmin = mel.get("fmin") or 0
         fmax = mel.get("fmax") or self.model_sr / 2
         basis = librosa_mel_fn(self.model_sr, n_fft, int(mel["num_mels"]), fmin, fmax)
-        self.mel = _native.MelTransform(n_fft, self.hop, win, self.pad, basis, mag_eps=1e-9, log_floor=float(mel.get("clip_val", 1e-5)))
+        self.mel = _native.MelTransform(n_fft, self.hop, win, self.pad, basis, mag_eps=1e-9, log_floor=float(mel.get("clip_val", 1e-5)),
+                                        device=self.device)
         # weights: the GEMM operands packed once for K11, the rest as they are
         self.w, self.a = {}, {}
         for k, v in w.items():

@@ -73,10 +73,9 @@ def _transform(n_fft, hop_size, win_size, mel_key, device):
     cached handle up in the training loop does not hash half a megabyte of filter bank per call."""
     key = (n_fft, hop_size, win_size, mel_key, str(device))
     if key not in _transforms:
-        with torch.cuda.device(device):
-            m = _basis(n_fft, *mel_key) if mel_key is not None else np.zeros((1, n_fft // 2 + 1), dtype=np.float32)
-            _transforms[key] = _native.MelTransform(n_fft, hop_size, win_size, int((n_fft - hop_size) / 2), m, mag_eps=1e-6,
-                                                    log_floor=1e-5)
+        m = _basis(n_fft, *mel_key) if mel_key is not None else np.zeros((1, n_fft // 2 + 1), dtype=np.float32)
+        _transforms[key] = _native.MelTransform(n_fft, hop_size, win_size, int((n_fft - hop_size) / 2), m, mag_eps=1e-6,
+                                                log_floor=1e-5, device=device)
     return _transforms[key]
 
 

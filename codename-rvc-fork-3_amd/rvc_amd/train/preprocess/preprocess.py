@@ -108,10 +108,8 @@ class PreProcess:
         try:
             audio = load_audio(path, self.sr, device=self.device)
             audio_length = len(audio) / self.sr                       # librosa.get_duration
-            with torch.cuda.device(self.device):
-                x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float64)).to(self.device)
-                self._process_uploaded(x, idx0, sid, cut_preprocess, process_effects, noise_reduction, chunk_len, overlap_len,
-                                       debug_taps)
+            x = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float64)).to(self.device)
+            self._process_uploaded(x, idx0, sid, cut_preprocess, process_effects, noise_reduction, chunk_len, overlap_len, debug_taps)
         except Exception as error:
             print(f"Error processing audio: {error}")
         return audio_length
