@@ -183,6 +183,9 @@ SYMBOLS = {
     "rvc_frame_rms_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "rvc_slice_export_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
                                      c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "rvc_spectral_gate_params": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_double), c_void_p, c_void_p]),
+    "rvc_spectral_gate_workspace_bytes": (c_int, [c_int64, c_int, c_int64, c_int64, POINTER(c_size_t)]),
+    "rvc_spectral_gate_f32": (c_int, [c_void_p, c_int64, c_int, c_float, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -614,6 +617,35 @@ def slice_export(x: torch.Tensor, bounds, up: int, down: int, h: torch.Tensor):
           seg_ptr + 16 * n_seg + 8 * (n_seg + 1), n_seg, up, down, h.data_ptr(), h.numel(),
           full.data_ptr() or seg_ptr, full.numel(), lo.data_ptr() or seg_ptr, lo.numel())
     return full, lo, off_full.tolist(), off_lo.tolist()
+
+
+# ---- K18 -----------------------------------------------------------------------------------------
+def spectral_gate_params(sr: int):
+    """-> (nf, nt, b, freq_taps[nf + 1], time_taps[nt + 1]): the constants rvc_spectral_gate_f32 derives from `sr` on the host
+    (float64) -- the half-widths of the mask smoothing filter, the smoother's coefficient and the filter's normalised 1-D factors
+    by distance from the centre.  No device access."""
+    import numpy as np
+    nf, nt, b = c_int(), c_int(), ctypes.c_double()
+    ft, tt = np.zeros(51, dtype=np.float64), np.zeros(51, dtype=np.float64)
+    _check(_lib.rvc_spectral_gate_params(int(sr), ctypes.byref(nf), ctypes.byref(nt), ctypes.byref(b), ft.ctypes.data, tt.ctypes.data),
+           "rvc_spectral_gate_params")
+    return nf.value, nt.value, b.value, ft[:nf.value + 1].copy(), tt[:nt.value + 1].copy()
+
+
+def spectral_gate(y: torch.Tensor, sr: int, prop_decrease: float = 1.0, chunk_size: int = 600000, padding: int = 30000) -> torch.Tensor:
+    """The non-stationary spectral gate of include/rvc_amd.h (K18) over y: 1-D float32 on the device -> float32 [n] on the same
+    device, enqueued on its current stream."""
+    if not torch.is_tensor(y) or y.dim() != 1:
+        raise NativeError("spectral_gate wants a 1-D float32 HBM tensor")
+    y = _dev_f32(y, "y")
+    out = torch.empty_like(y)
+    n = y.numel()
+    dims = (n, int(sr), int(chunk_size), int(padding))
+    ws = _workspace("spectral_gate", y.device, "rvc_spectral_gate_workspace_bytes", *dims)
+    # an empty tensor has no storage: hand the library an address it never dereferences (n == 0 touches nothing)
+    _call("rvc_spectral_gate_f32", y.device, y.data_ptr() or ws.data_ptr(), n, int(sr), float(prop_decrease), int(chunk_size), int(padding),
+          out.data_ptr() or ws.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
 
 
 # ---- K5 ------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """``VoiceConverter`` -- orchestration around the pipeline with the reference's surface
-(rvc/infer/infer.py:41-493).  File decoding/resampling, noise reduction and the pedalboard effects are out of
-scope: ``convert_audio`` reads WAV files of any rate / channel count / PCM or float encoding
+(rvc/infer/infer.py:41-493).  File decoding/resampling and the pedalboard effects are out of
+scope; ``clean_audio`` runs the native spectral gate (rvc_amd.lib.noise_reduce, K18).
+``convert_audio`` reads WAV files of any rate / channel count / PCM or float encoding
 (rvc_amd.lib.audio: own RIFF parser, device-side polyphase resampler to 16 kHz in place of soxr) and writes 16-bit WAV, or
 use ``convert_array`` with a NumPy signal.
 """
@@ -19,6 +20,7 @@ from rvc_amd.infer.pipeline import Pipeline as VC
 from rvc_amd.lib.audio import load_audio_infer
 from rvc_amd.lib.algorithm.synthesizers import Synthesizer
 from rvc_amd.lib.hubert import HubertModelWithFinalProj
+from rvc_amd.lib.noise_reduce import reduce_noise
 from rvc_amd.lib.tools.split_audio import merge_audio, process_audio
 
 
@@ -104,13 +106,24 @@ class VoiceConverter:
             self.vc = VC(self.tgt_sr, self.config)
             self.n_spk = self.cpt["config"][-3]
 
+    # ---- noise removal (infer.py:77-93) ----
+    @staticmethod
+    def remove_audio_noise(data, sr, reduction_strength=0.7):
+        """The spectral gate over a converted waveform (NumPy array or device tensor, same kind out); None when it fails."""
+        try:
+            return reduce_noise(y=data, sr=sr, prop_decrease=reduction_strength)
+        except Exception as error:
+            print(f"An error occurred removing audio noise: {error}")
+            return None
+
     # ---- conversion ----
     def convert_array(self, audio: np.ndarray, *, index_path: str = "", pitch: int = 0, f0_file=None,
                       f0_method: str = "rmvpe", index_rate: float = 0.75, volume_envelope: float = 1,
                       protect: float = 0.5, hop_length: int = 128, f0_autotune: bool = False,
                       f0_autotune_strength: float = 1, filter_radius: float = 3.0, sid: int = 0, noise_seed=None,
-                      split_audio: bool = False):
-        """The array-level core of convert_audio (infer.py:262-311): 16 kHz float array in, float32 @tgt_sr out."""
+                      split_audio: bool = False, clean_audio: bool = False, clean_strength: float = 0.5):
+        """The array-level core of convert_audio (infer.py:262-325): 16 kHz float array in, float32 @tgt_sr out; clean_audio runs
+        remove_audio_noise over the result on the same stream and keeps the uncleaned audio when that fails."""
         if torch.is_tensor(audio):  # HBM-resident entry: same peak limiting on the device
             audio = audio.to(device=self.config.device, dtype=torch.float64)
             audio_max = audio.abs().max() / 0.95
@@ -132,8 +145,12 @@ class VoiceConverter:
                                     hop_length=hop_length, f0_autotune=f0_autotune,
                                     f0_autotune_strength=f0_autotune_strength, f0_file=f0_file, noise_seed=noise_seed)
 
+        def done(out):   # infer.py:320-325
+            cleaned = self.remove_audio_noise(out, self.tgt_sr, clean_strength) if clean_audio else None
+            return out if cleaned is None else cleaned
+
         if not split_audio:
-            return run(audio)
+            return done(run(audio))
         # infer.py:283-318: cut at silences (host, on the 16 kHz input), convert the chunks, put them back on the time line
         host = audio.cpu().numpy() if torch.is_tensor(audio) else audio
         chunks, intervals = process_audio(host, 16000)
@@ -144,7 +161,7 @@ class VoiceConverter:
             converted.append(out.cpu().numpy() if torch.is_tensor(out) else out)
             print(f"Converted audio chunk {len(converted)}")
         merged = merge_audio(chunks, converted, intervals, 16000, self.tgt_sr)
-        return torch.from_numpy(merged).to(audio.device) if torch.is_tensor(audio) else merged
+        return done(torch.from_numpy(merged).to(audio.device) if torch.is_tensor(audio) else merged)
 
     def convert_batch(self, audios, *, inflight: int = 3, **kwargs):
         """Convert a list of 16 kHz utterances with ``inflight`` of them on the GPU at a time, each on its own HIP stream
@@ -263,9 +280,8 @@ class VoiceConverter:
         try:
             start_time = time.time()
             print(f"Converting audio '{audio_input_path}'...")
-            if clean_audio or post_process or export_format != "WAV":
-                raise NotImplementedError("clean_audio / post_process / non-WAV export are outside the hot path "
-                                          "(SURVEY §2 items 2, 9)")
+            if post_process or export_format != "WAV":
+                raise NotImplementedError("post_process / non-WAV export are outside the hot path (SURVEY §2 items 2, 9)")
             audio = load_audio_infer(audio_input_path, 16000, device=self.config.device)   # infer.py:257-260
             if not self.hubert_model or embedder_model != self.last_embedder_model:
                 self.load_hubert(embedder_model, embedder_model_custom)
@@ -276,7 +292,8 @@ class VoiceConverter:
                                            f0_method=f0_method, index_rate=index_rate,
                                            volume_envelope=volume_envelope, protect=protect, hop_length=hop_length,
                                            f0_autotune=f0_autotune, f0_autotune_strength=f0_autotune_strength,
-                                           filter_radius=filter_radius, sid=sid, split_audio=split_audio)
+                                           filter_radius=filter_radius, sid=sid, split_audio=split_audio,
+                                           clean_audio=clean_audio, clean_strength=clean_strength)
             _write_wav(audio_output_path, audio_opt, self.tgt_sr)
             print(f"Conversion completed at '{audio_output_path}' in {time.time() - start_time:.2f} seconds.")
         except Exception as error:

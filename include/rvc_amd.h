@@ -688,6 +688,52 @@ int rvc_slice_export_f32(const double *x_dev, int64_t n, const int64_t *bounds_h
                          const double *h_dev, int64_t n_taps, float *full_dev, int64_t n_full, float *lo_dev, int64_t n_lo,
                          void *stream);
 
+/* ---- K18: clean_audio, a non-stationary spectral gate (csrc/spectralgate.hip) ---------------------------------- *
+ * Replaces `noisereduce.reduce_noise(y=audio, sr=sr, prop_decrease=p)` (rvc/infer/infer.py:77-93) in its default,
+ * stationary=False form.  noisereduce absent: parity with the wheel unpinned -- the algorithm below IS the contract, and the
+ * yardstick is its float64 SciPy restatement in tests/spectral_gate_ref.py.
+ *
+ * Constants: n_fft = win = 1024, hop = 256, time_constant_s = 2, thresh = 2, slope = 10, freq_mask_smooth_hz = 500,
+ * time_mask_smooth_ms = 50.  Chunks: [0, n) when n <= chunk_size, else [s, min(s + chunk_size, n)) for s = 0, chunk_size, ...;
+ * chunk [s, e) is filtered inside the buffer c = y[s - padding : e + padding] (zeros outside [0, n)), L = e - s + 2 padding, and
+ * out[s:e] = filtered[padding : padding + e - s].  Chunks are independent.  Filtering one buffer:
+ *   1. S = STFT of c: periodic hann(1024), hop 256, 512 zeros on each side, F = L / 256 + 1 frames (scipy.signal.stft,
+ *      boundary='zeros', padded=False; its 1 / sum(win) scaling cancels against step 7 and is not applied);
+ *   2. A = |S|;
+ *   3. M = the one-pole smoother f[t] = b A[t] + (1 - b) f[t - 1] run forward, then backward over f, along time per bin, each
+ *      pass starting as if the sample before its first equalled it (scipy.signal.filtfilt([b], [1, b - 1], padtype=None));
+ *      t = 2 sr / 256, b = (sqrt(1 + 4 t^2) - 1) / (2 t^2);
+ *   4. mask = 1 / (1 + exp(-((A - M) / M - 2) * 10)); a bin that is zero in every frame (M == 0) takes (A - M) / M = 0: its mask
+ *      is finite and its output zero, where noisereduce yields NaN for digital silence;
+ *   5. mask = the 2-D convolution (mode "same", zeros outside) of mask with outer(ramp(nf), ramp(nt)) / sum, applied as its two
+ *      1-D factors; nf = int(500 / (sr / 512)) bins, nt = int(50 / ((256 / sr) * 1000)) frames, ramp(k)[d] = (k + 1 - |d|) / (k + 1)
+ *      for |d| <= k (11 x 19 points at 48 kHz); nf, nt and b are evaluated on the host in float64 with exactly these expressions;
+ *   6. mask = mask * prop_decrease + (1 - prop_decrease);
+ *   7. x = the inverse rDFT of S * mask per frame (imaginary parts of the DC and Nyquist bins ignored), times the window,
+ *      overlap-added, divided by the running sum of win^2 of the frames that cover the sample, trimmed by 512 on each side:
+ *      L - L % 256 samples; filtered = x followed by zeros (that tail lies in the padding whenever padding >= 256).
+ * Arithmetic: fp32 throughout, except the state of the recurrence of step 3, which is float64 (M itself is kept as fp32).  Both
+ * transforms are dense DFTs on the exact-fp32 matrix cores: a dot product is summed as fmaf chains in index order over
+ * consecutive ranges of its terms -- 16 chains of 64 samples forward, 4 chains of 288 spectral rows inverse -- whose sums are
+ * added in range order.  Every output sample sums its <= 4 frames in frame order, nothing is accumulated atomically: two
+ * calls give identical bits, on any stream.  Against the float64 restatement the output deviates by 4 to 10 times what SciPy's
+ * own float32 path does (4e-7 .. 8e-7 absolute on a signal of amplitude 0.5).
+ *
+ * rvc_spectral_gate_params: nf, nt, b of `sr` and, where the pointers are not NULL, the normalised 1-D factors of step 5 as
+ *   freq_taps[0 .. nf] / time_taps[0 .. nt] (the weight at distance |d|; host memory, room for 51 doubles each).  No device access.
+ * rvc_spectral_gate_workspace_bytes: the scratch one call needs: 17.5 KiB per frame of min(number of chunks, chunks per group)
+ *   chunks, where a group holds as many whole chunks as fit into 8192 frames (at least one).  It depends on chunk_size and
+ *   padding but, once the signal fills one group, not on n: longer signals are walked group by group.  0 when n == 0.
+ * rvc_spectral_gate_f32: y_dev[n] -> out_dev[n] (fp32, must not alias), asynchronous on `hip_stream` (the library's usual
+ *   trailing `void *stream` argument).  Refused with an error, before anything touches the device: a NULL y_dev, out_dev or
+ *   workspace_dev; n < 0; sr outside [5120, 256000] (nt or nf would be 0); prop_decrease outside [0, 1]; chunk_size < 1;
+ *   padding < 0; min(chunk_size, n) + 2 padding above 2^27 samples; workspace_bytes below the size query's answer.  n == 0
+ *   succeeds and writes nothing.  The DFT bases and the window are uploaded once per device, on the first call there. */
+int rvc_spectral_gate_params(int sr, int *nf, int *nt, double *b, double *freq_taps, double *time_taps);
+int rvc_spectral_gate_workspace_bytes(int64_t n, int sr, int64_t chunk_size, int64_t padding, size_t *bytes);
+int rvc_spectral_gate_f32(const float *y_dev, int64_t n, int sr, float prop_decrease, int64_t chunk_size, int64_t padding,
+                          float *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
