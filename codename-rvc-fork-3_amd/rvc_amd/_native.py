@@ -186,6 +186,9 @@ SYMBOLS = {
     "rvc_spectral_gate_params": (c_int, [c_int, POINTER(c_int), POINTER(c_int), POINTER(ctypes.c_double), c_void_p, c_void_p]),
     "rvc_spectral_gate_workspace_bytes": (c_int, [c_int64, c_int, c_int64, c_int64, POINTER(c_size_t)]),
     "rvc_spectral_gate_f32": (c_int, [c_void_p, c_int64, c_int, c_float, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_formant_shift_workspace_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
+    "rvc_formant_shift_f32": (c_int, [c_void_p, c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -645,6 +648,21 @@ def spectral_gate(y: torch.Tensor, sr: int, prop_decrease: float = 1.0, chunk_si
     # an empty tensor has no storage: hand the library an address it never dereferences (n == 0 touches nothing)
     _call("rvc_spectral_gate_f32", y.device, y.data_ptr() or ws.data_ptr(), n, int(sr), float(prop_decrease), int(chunk_size), int(padding),
           out.data_ptr() or ws.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
+
+
+# ---- K19 -----------------------------------------------------------------------------------------
+def formant_shift(x: torch.Tensor, sr: int, quefrency_s: float, distortion: float, group_frames: int = 0) -> torch.Tensor:
+    """The formant shifter of include/rvc_amd.h (K19) over x: 1-D float32 on the device, at least 1024 samples -> float32 [n] on
+    the same device, enqueued on its current stream."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise NativeError("formant_shift wants a 1-D float32 HBM tensor")
+    x = _dev_f32(x, "x")
+    n = x.numel()
+    ws = _workspace("formant_shift", x.device, "rvc_formant_shift_workspace_bytes", n, int(group_frames))
+    out = torch.empty_like(x)
+    _call("rvc_formant_shift_f32", x.device, x.data_ptr(), n, int(sr), float(quefrency_s), float(distortion), int(group_frames),
+          out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 

@@ -1,6 +1,7 @@
 """``VoiceConverter`` -- orchestration around the pipeline with the reference's surface
 (rvc/infer/infer.py:41-493).  File decoding/resampling and the pedalboard effects are out of
-scope; ``clean_audio`` runs the native spectral gate (rvc_amd.lib.noise_reduce, K18).
+scope; ``clean_audio`` runs the native spectral gate (rvc_amd.lib.noise_reduce, K18) and
+``formant_shifting`` the native formant shifter (rvc_amd.lib.formant_shift, K19).
 ``convert_audio`` reads WAV files of any rate / channel count / PCM or float encoding
 (rvc_amd.lib.audio: own RIFF parser, device-side polyphase resampler to 16 kHz in place of soxr) and writes 16-bit WAV, or
 use ``convert_array`` with a NumPy signal.
@@ -18,6 +19,7 @@ import torch
 from rvc_amd.configs.config import Config
 from rvc_amd.infer.pipeline import Pipeline as VC
 from rvc_amd.lib.audio import load_audio_infer
+from rvc_amd.lib.formant_shift import shift_formants
 from rvc_amd.lib.algorithm.synthesizers import Synthesizer
 from rvc_amd.lib.hubert import HubertModelWithFinalProj
 from rvc_amd.lib.noise_reduce import reduce_noise
@@ -121,9 +123,14 @@ class VoiceConverter:
                       f0_method: str = "rmvpe", index_rate: float = 0.75, volume_envelope: float = 1,
                       protect: float = 0.5, hop_length: int = 128, f0_autotune: bool = False,
                       f0_autotune_strength: float = 1, filter_radius: float = 3.0, sid: int = 0, noise_seed=None,
-                      split_audio: bool = False, clean_audio: bool = False, clean_strength: float = 0.5):
+                      split_audio: bool = False, clean_audio: bool = False, clean_strength: float = 0.5,
+                      formant_shifting: bool = False, formant_qfrency: float = 0.8, formant_timbre: float = 0.8):
         """The array-level core of convert_audio (infer.py:262-325): 16 kHz float array in, float32 @tgt_sr out; clean_audio runs
-        remove_audio_noise over the result on the same stream and keeps the uncleaned audio when that fails."""
+        remove_audio_noise over the result on the same stream and keeps the uncleaned audio when that fails; formant_shifting runs
+        shift_formants (K19) over the input on the same stream BEFORE the peak limiting, where load_audio_infer has it."""
+        if formant_shifting:        # utils.py:70-82
+            audio = audio.to(device=self.config.device, dtype=torch.float64) if torch.is_tensor(audio) else np.asarray(audio, dtype=np.float64)
+            audio = shift_formants(audio, 16000, formant_qfrency, formant_timbre, device=self.config.device)
         if torch.is_tensor(audio):  # HBM-resident entry: same peak limiting on the device
             audio = audio.to(device=self.config.device, dtype=torch.float64)
             audio_max = audio.abs().max() / 0.95
@@ -169,7 +176,8 @@ class VoiceConverter:
         and one utterance alone leaves the chip partly idle -- the 8-CU BiGRU, the 1.17-round first vocoder stage, ~1500
         small launches -- so interleaved utterances finish sooner than in sequence: 30.4 / 26.0 / 25.1-25.7 ms per 30 s
         utterance at 1 / 2 / 3 in flight (round 6, profiles/r06_inflight_sweep.txt; each one in flight keeps ~2.5 GB of workspaces).  Results keep the input
-        order; device tensors in give device tensors out (valid once this returns)."""
+        order; device tensors in give device tensors out (valid once this returns).  The keywords are convert_array's:
+        formant_shifting / formant_qfrency / formant_timbre and clean_audio / clean_strength run on the utterance's own stream."""
         import threading
         audios = list(audios)
         results = [None] * len(audios)
@@ -282,7 +290,7 @@ class VoiceConverter:
             print(f"Converting audio '{audio_input_path}'...")
             if post_process or export_format != "WAV":
                 raise NotImplementedError("post_process / non-WAV export are outside the hot path (SURVEY §2 items 2, 9)")
-            audio = load_audio_infer(audio_input_path, 16000, device=self.config.device)   # infer.py:257-260
+            audio = load_audio_infer(audio_input_path, 16000, device=self.config.device, **kwargs)   # infer.py:257-261
             if not self.hubert_model or embedder_model != self.last_embedder_model:
                 self.load_hubert(embedder_model, embedder_model_custom)
                 self.last_embedder_model = embedder_model

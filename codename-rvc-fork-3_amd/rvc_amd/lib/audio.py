@@ -114,13 +114,17 @@ def load_audio(file, sample_rate, device="cuda:0"):
 
 
 def load_audio_infer(file, sample_rate, device="cuda:0", **kwargs):
-    """rvc/lib/utils.py:53-85 (formant shifting -- stftpitchshift, third party -- is outside the hot path)."""
-    if kwargs.get("formant_shifting", False):
-        raise RuntimeError("An error occurred loading the audio: formant shifting (stftpitchshift) is not part of this build")
+    """rvc/lib/utils.py:53-85; formant_shifting=True runs the native formant shifter (rvc_amd.lib.formant_shift, K19) over the
+    resampled signal with formant_qfrency / formant_timbre (defaults 0.8, 0.8) in place of stftpitchshift."""
     try:
         file = file.strip(" ").strip('"').strip("\n").strip('"').strip(" ")
         if not os.path.isfile(file):
             raise FileNotFoundError(f"File not found: {file}")
-        return _load(file, sample_rate, device)
+        audio = _load(file, sample_rate, device)
+        if kwargs.get("formant_shifting", False):
+            from rvc_amd.lib.formant_shift import shift_formants
+            audio = shift_formants(audio, sample_rate, kwargs.get("formant_qfrency", 0.8), kwargs.get("formant_timbre", 0.8),
+                                   device=device)
+        return np.asarray(audio, dtype=np.float64).flatten()
     except Exception as error:
         raise RuntimeError(f"An error occurred loading the audio: {error}")

@@ -734,6 +734,52 @@ int rvc_spectral_gate_workspace_bytes(int64_t n, int sr, int64_t chunk_size, int
 int rvc_spectral_gate_f32(const float *y_dev, int64_t n, int sr, float prop_decrease, int64_t chunk_size, int64_t padding,
                           float *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* ---- K19: formant_shifting, a cepstral spectral-envelope edit (csrc/formant.hip) --------------------------------- *
+ * Replaces `stftpitchshift.StftPitchShift(1024, 32, sr).shiftpitch(audio, factors=1, quefrency=formant_qfrency * 1e-3,
+ * distortion=formant_timbre)` (rvc/lib/utils.py:70-82) on the 16 kHz input.  stftpitchshift absent: parity with the wheel
+ * unpinned -- the algorithm below IS the contract, and the yardstick is its float64 SciPy restatement in
+ * tests/formant_shift_ref.py.
+ *
+ * Input x[n], fp32, at sr.  Constants: N = 1024, H = 32, B = 513.  Q = int(quefrency_s * sr), d = distortion.
+ *   1. Frames.  F = (n - N) / H + 1 (integer division); frame t is x[tH .. tH + N), no centre padding, times the periodic Hann
+ *      window w[i] = 0.5 - 0.5 cos(2 pi i / N); forward rDFT scaled by 1 / N: S[t][k], k < B.
+ *   2. Envelope, only when Q > 0, per frame.  L[k] = log10 |S[k]|.  Cepstrum c[q] = L[0] + (-1)^q L[512] +
+ *      2 sum_{k=1..511} L[k] cos(2 pi q k / N) (irfft(L, norm="forward")).  Lifter: keep c[0], double c[1 .. Q-1], keep c[Q]
+ *      once, zero above.  E[k] = 10 ** ((1 / N) sum_q c'[q] cos(2 pi q k / N)) (rfft(c', norm="forward").real).  A value is "not
+ *      normal" when it is inf, NaN or below the smallest normal number of its type.  mask1 = notnormal(E).  G[k] = |S[k]| / E[k],
+ *      and 0 where mask1.
+ *   3. Warp.  If d == 1, E' = E.  Otherwise E[mask1] = 0 and E is resampled linearly: m = int(B * d); for i < min(B, m):
+ *      pos = i * (B / m), j = trunc(pos), f = pos - j, E'[i] = f E[j+1] + (1 - f) E[j] when j < B - 1, else 0; E'[i] = 0 for
+ *      i >= min(B, m).  mask2 = notnormal(E').  G[k] *= E'[k], and 0 where mask2.  So for d < 1 the bins from int(513 d) up are
+ *      silenced (the wheel's behaviour).  With Q == 0, G = |S|: the call is only the STFT round trip.
+ *   4. Output spectrum Y = G S / |S|, and 0 where |S| == 0.  (The wheel's phase-vocoder encode / decode with factors = 1 is the
+ *      identity on the phase modulo 2 pi and is not built.)
+ *   5. Inverse.  Unscaled inverse rDFT of Y (irfft(norm="forward"): DC and Nyquist counted once, their imaginary parts ignored),
+ *      times w H / sum(w^2), overlap-added at tH.  Output sample s is the sum of its <= 32 frames in frame order, as a gather: no
+ *      atomics, identical bits on every call.  Samples at or beyond (F - 1) H + N are 0.  The output has length n.  The tapered
+ *      first and last 1024 samples and the dead tail are the wheel's own edge behaviour.
+ * Degenerate frames: a frame with any bin of magnitude exactly 0 (digital silence) has L = -inf, its whole envelope is NaN, every
+ * bin is masked and the frame contributes zeros -- zeros on the device too, never NaN or inf.
+ * Arithmetic: both transforms are K18's dense DFTs on the exact-fp32 matrix cores (16 fmaf chains of 64 samples forward, 4 of 288
+ * spectral rows inverse, added in range order); |S|, L, c, E, E' and G are float64 on the device, cosines from a 1024-entry
+ * float64 table at (q k) mod 1024, the warp positions float64 with exactly the expressions of step 3; "not normal" is tested on
+ * the fp32 rounding of E and E'; the gain ratio G / |S| and everything after it are fp32.  Against the float64 restatement the
+ * output deviates by 1 to 5 times what SciPy's own float32 path does on the tests' cases (1e-7 .. 6e-7 absolute at a peak of
+ * 0.3), and by 15 times on a 30 s signal.
+ *
+ * rvc_formant_shift_workspace_bytes: the scratch one call needs: 15.25 KiB per frame of min(F, group) frames rounded up to 128,
+ *   plus 141 824 bytes; group = group_frames, or 8192 when that is 0.  Once the signal fills one group it does not depend on n:
+ *   longer signals are walked group by group, the 31 last inverse frames of a group kept for the next one's overlap-add, so the
+ *   output does not depend on group_frames either.  Refuses n and group_frames as the forward call does.
+ * rvc_formant_shift_f32: x_dev[n] -> out_dev[n], asynchronous on `hip_stream` (the library's usual trailing `void *stream`
+ *   argument).  Refused with an error, before anything touches the device: a NULL x_dev, out_dev or workspace_dev;
+ *   out_dev == x_dev; n < 1024 (the wheel cannot frame it either); n above 2^27; sr < 1; quefrency_s < 0, or Q > 511; distortion
+ *   not finite or <= 0, or int(513 * distortion) < 1; group_frames neither 0 nor a multiple of 128 in [128, 8192];
+ *   workspace_bytes below the size query's answer. */
+int rvc_formant_shift_workspace_bytes(int64_t n, int group_frames, size_t *bytes);
+int rvc_formant_shift_f32(const float *x_dev, int64_t n, int sr, double quefrency_s, double distortion, int group_frames,
+                          float *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
