@@ -189,6 +189,13 @@ SYMBOLS = {
     "rvc_formant_shift_workspace_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
     "rvc_formant_shift_f32": (c_int, [c_void_p, c_int64, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "rvc_mrstft_sums_workspace_bytes": (c_int, [c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_size_t)]),
+    "rvc_mrstft_sums_f32": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, ctypes.c_double,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_si_sdr_sums_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "rvc_si_sdr_sums_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_mean_abs_diff_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "rvc_mean_abs_diff_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -667,6 +674,56 @@ def formant_shift(x: torch.Tensor, sr: int, quefrency_s: float, distortion: floa
 
 
 # ---- K5 ------------------------------------------------------------------------------------------
+def _signal_pair(x: torch.Tensor, y: torch.Tensor, what: str):
+    if x.dim() != 1 or y.dim() != 1 or x.shape != y.shape:
+        raise NativeError(f"{what} wants two 1-D signals of equal length, got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    _device(x, y)
+    return _dev_f32(x, f"{what}: x"), _dev_f32(y, f"{what}: y")
+
+
+def mrstft_sums(x: torch.Tensor, y: torch.Tensor, fft_sizes, hop_sizes, win_lengths, eps: float = 1e-8) -> torch.Tensor:
+    """The multi-resolution STFT sums of include/rvc_amd.h (K20) of the prediction x and the target y (1-D float32 on the device)
+    -> float64 [n_res, 4] on the device: sum (ymag - xmag)^2, sum ymag^2, sum |log xmag - log ymag| and the number of terms."""
+    x, y = _signal_pair(x, y, "mrstft_sums")
+    n_res = len(fft_sizes)
+    if not (len(hop_sizes) == len(win_lengths) == n_res):
+        raise NativeError("mrstft_sums: fft_sizes, hop_sizes and win_lengths must have one entry per resolution")
+    arr = [(c_int * max(n_res, 1))(*[int(v) for v in vals]) for vals in (fft_sizes, hop_sizes, win_lengths)]
+    ws = _workspace("mrstft_sums", x.device, "rvc_mrstft_sums_workspace_bytes", x.numel(), *arr, n_res)
+    out = torch.empty(max(n_res, 1), 4, dtype=torch.float64, device=x.device)
+    _call("rvc_mrstft_sums_f32", x.device, x.data_ptr(), y.data_ptr(), x.numel(), *arr, n_res, float(eps), out.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return out
+
+
+def si_sdr_sums(preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """The five SI-SDR sums of include/rvc_amd.h (K20) -> float64 [5] on the device: sum p, sum t, and of the centred signals
+    sum pc tc, sum tc^2, sum pc^2."""
+    preds, target = _signal_pair(preds, target, "si_sdr_sums")
+    ws = _workspace("si_sdr_sums", preds.device, "rvc_si_sdr_sums_workspace_bytes", preds.numel())
+    out = torch.empty(5, dtype=torch.float64, device=preds.device)
+    _call("rvc_si_sdr_sums_f32", preds.device, preds.data_ptr(), target.data_ptr(), preds.numel(), out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
+
+
+def mean_abs_diff_sum(a: torch.Tensor, b: torch.Tensor, min_t: int) -> torch.Tensor:
+    """sum |a[r, c] - b[r, c]| over the first min_t columns of two float32 matrices on the device with as many rows (each may be
+    a column slice of a wider matrix: the row stride is passed on) -> float64 [1] on the device (K20)."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise NativeError(f"mean_abs_diff_sum wants two matrices with as many rows, got shapes {tuple(a.shape)} and {tuple(b.shape)}")
+    if min_t > min(a.shape[1], b.shape[1]):
+        raise NativeError(f"mean_abs_diff_sum: min_t = {min_t} exceeds a width ({a.shape[1]}, {b.shape[1]})")
+    _device(a, b)
+    a, b = (t if t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] else
+            _dev_f32(t, "mean_abs_diff_sum: matrix") for t in (a, b))
+    rows = a.shape[0]
+    ws = _workspace("mean_abs_diff", a.device, "rvc_mean_abs_diff_workspace_bytes", rows, int(min_t))
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    _call("rvc_mean_abs_diff_f32", a.device, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), rows, int(min_t), out.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return out
+
+
 def bigru_forward(gi: torch.Tensor, whh_t: torch.Tensor, bhh: torch.Tensor, multi_cu: bool = True) -> torch.Tensor:
     """gi [B,T,2,768] (input projections) -> [B,T,512]; see include/rvc_amd.h."""
     gi, whh_t, bhh = _dev_f32(gi, "gi"), _dev_f32(whh_t, "whh_t"), _dev_f32(bhh, "bhh")
