@@ -196,6 +196,10 @@ SYMBOLS = {
     "rvc_si_sdr_sums_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rvc_mean_abs_diff_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "rvc_mean_abs_diff_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_sola_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "rvc_sola_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                             c_void_p]),
+    "rvc_stream_window_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -671,6 +675,49 @@ def formant_shift(x: torch.Tensor, sr: int, quefrency_s: float, distortion: floa
     _call("rvc_formant_shift_f32", x.device, x.data_ptr(), n, int(sr), float(quefrency_s), float(distortion), int(group_frames),
           out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
+
+
+# ---- K21 -----------------------------------------------------------------------------------------
+def _vec_f32(t, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dim() != 1:
+        raise NativeError(f"{name} must be a 1-D float32 HBM tensor")
+    if not t.is_contiguous():   # an in/out argument cannot be replaced by a copy
+        raise NativeError(f"{name} must be contiguous")
+    return _dev_f32(t, name)
+
+
+def stream_window(hist: torch.Tensor, block: torch.Tensor) -> torch.Tensor:
+    """rvc_stream_window_f32 (K21): -> window = [hist | block], a new float32 tensor; `hist` (1-D float32 on the device, updated in
+    place) then holds the window's last len(hist) samples.  One launch on the device's current stream."""
+    hist, block = _vec_f32(hist, "hist"), _vec_f32(block, "block")
+    dev = _device(hist, block)
+    window = torch.empty(hist.numel() + block.numel(), dtype=torch.float32, device=dev)
+    if window.numel() == 0:
+        return window
+    # an empty tensor has no storage: hand the library an address it never dereferences
+    _call("rvc_stream_window_f32", dev, hist.data_ptr() or block.data_ptr(), hist.numel(), block.data_ptr() or hist.data_ptr(),
+          block.numel(), window.data_ptr())
+    return window
+
+
+def sola(infer: torch.Tensor, buf: torch.Tensor, fade_in: torch.Tensor, search: int, block: int, offset: torch.Tensor = None):
+    """rvc_sola_f32 (K21): infer [block + len(buf) + search], buf [xfade] (the saved tail, updated in place) and fade_in [xfade],
+    1-D float32 on the device -> (out float32 [block], offset int32 [1] on the device: the chosen lag; pass `offset` to reuse one).
+    Two launches on the device's current stream; nothing is read back."""
+    infer, buf, fade_in = _vec_f32(infer, "infer"), _vec_f32(buf, "buf"), _vec_f32(fade_in, "fade_in")
+    dev = _device(infer, buf, fade_in, offset)
+    xfade, search, block = buf.numel(), int(search), int(block)
+    if fade_in.numel() != xfade:
+        raise NativeError(f"sola: fade_in has {fade_in.numel()} samples, buf {xfade}")
+    if offset is None:
+        offset = torch.empty(1, dtype=torch.int32, device=dev)
+    elif not (offset.is_cuda and offset.dtype == torch.int32 and offset.numel() == 1):
+        raise NativeError("sola: offset must be an int32 HBM tensor of one element")
+    ws = _workspace("sola", dev, "rvc_sola_workspace_bytes", xfade, search)
+    out = torch.empty(max(block, 0), dtype=torch.float32, device=dev)
+    _call("rvc_sola_f32", dev, infer.data_ptr(), infer.numel(), buf.data_ptr(), fade_in.data_ptr(), xfade, search, block,
+          out.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel())
+    return out, offset
 
 
 # ---- K5 ------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ scope; ``clean_audio`` runs the native spectral gate (rv
 ``formant_shifting`` the native formant shifter (rvc_amd.lib.formant_shift, K19).
 ``convert_audio`` reads WAV files of any rate / channel count / PCM or float encoding
 (rvc_amd.lib.audio: own RIFF parser, device-side polyphase resampler to 16 kHz in place of soxr) and writes 16-bit WAV, or
-use ``convert_array`` with a NumPy signal.
+use ``convert_array`` with a NumPy signal.  ``open_stream`` converts block by block (rvc_amd.infer.realtime, K21; not in the reference).
 """
 from __future__ import annotations
 
@@ -53,6 +53,7 @@ class VoiceConverter:
         self.dec_arithmetic = "exact"   # "fp16x2": the vocoder's 128- / 256-channel ResBlock convs on error-corrected fp16 pairs (faster, ~2^-22 per product); not with dec_weight_dtype = "bf16"
         self.trim_vocoder_pad = True    # the vocoder skips the padded second on each side that Pipeline.pipeline trims off again (rvc_decoder_forward_window); False: the whole padded segment (A/B runs)
         self.branch_streams = 0         # Decoder.set_branch_parallel for convert_batch: 0 = every vocoder launch on the utterance's stream, -1 = one side stream per ResBlock branch
+        self._streams = set()           # the open ConversionStreams (open_stream): they hold this converter's model
 
     # ---- embedder (infer.py:64-74; file layout rvc/lib/utils.py:96-146) ----
     def load_hubert(self, embedder_model: str, embedder_model_custom: str = None):
@@ -67,8 +68,14 @@ class VoiceConverter:
         self.hubert_model = HubertModelWithFinalProj(sd, device=self.config.device).float().eval()
 
     # ---- model (infer.py:416-493) ----
+    def _refuse_model_change(self, what):
+        if getattr(self, "_streams", None):
+            raise RuntimeError(f"{what}: this converter has {len(self._streams)} open stream(s) on {self.loaded_model!r}; close them "
+                               "first, or use another VoiceConverter for the second model")
+
     def get_vc(self, weight_root, sid):
         if not self.loaded_model or self.loaded_model != weight_root:
+            self._refuse_model_change(f"loading {weight_root!r}")
             self.load_model(weight_root)
             if self.cpt is not None:
                 self.setup_network()
@@ -80,6 +87,7 @@ class VoiceConverter:
 
     def load_checkpoint_dict(self, cpt: dict):
         """Same as get_vc() for an in-memory checkpoint dict (extract_model.py:56-107 format)."""
+        self._refuse_model_change("load_checkpoint_dict")
         self.cpt = dict(cpt)
         self.cpt["config"] = list(cpt["config"])
         self.setup_network()
@@ -307,6 +315,33 @@ class VoiceConverter:
         except Exception as error:
             print(f"An error occurred during audio conversion: {error}")
             print(traceback.format_exc())
+
+    # ---- streaming (rvc_amd/infer/realtime.py; the reference has no such mode) ----
+    def open_stream(self, model_path=None, index_path: str = "", **kwargs):
+        """A live, block-by-block conversion on this converter's model:
+
+            stream = vc.open_stream(model_path, index_path, block_ms=250, context_ms=1000, crossfade_ms=50, search_ms=10)
+            out = stream.push(block)      # stream.block_samples @16 kHz -> stream.block_out samples @ stream.sr
+
+        model_path: a checkpoint file, as convert_audio takes it (None: the model this converter has loaded).  block_ms /
+        context_ms / crossfade_ms / search_ms: multiples of 10; every push converts the last context + crossfade + search ms of
+        input in front of the new block and joins the result to the previous block with SOLA on the device (K21): slide by up to
+        search_ms to the best normalised correlation, crossfade over crossfade_ms.  stream.latency_ms = block + crossfade + search.
+        pitch, f0_method, index_rate, protect, filter_radius, sid, volume_envelope, hop_length, f0_autotune,
+        f0_autotune_strength, noise_seed, embedder_model, embedder_model_custom: as in convert_audio / convert_array.
+        ValueError: a length that is no multiple of 10 ms, crossfade_ms > block_ms, a context too short for the join, a block of
+        the wrong length.  NotImplementedError: split_audio, f0_file, clean_audio, formant_shifting, post_process, resample_sr
+        (they work on a whole utterance).  While a stream is open the converter refuses to load another model (RuntimeError).
+        Streams of one converter are pushed from one thread at a time (see ConversionStream)."""
+        from rvc_amd.infer import realtime
+        return realtime.open_stream(self, model_path, index_path, **kwargs)
+
+    def convert_audio_stream(self, audio_input_path: str, audio_output_path: str, model_path=None, index_path: str = "", **kwargs):
+        """Feed a WAV file through open_stream(model_path, index_path, **kwargs) block by block (the last block zero-padded) and
+        write the result, trimmed to the input's duration, as 16-bit WAV.  -> {"blocks", "block_ms", "push_ms": [one per push],
+        "median_ms", "max_ms"}: the pushes timed with HIP events on the stream they run on.  Raises what open_stream and push raise."""
+        from rvc_amd.infer import realtime
+        return realtime.convert_audio_stream(self, audio_input_path, audio_output_path, model_path, index_path, **kwargs)
 
     def convert_audio_batch(self, audio_input_paths: str, audio_output_path: str, **kwargs):
         """infer.py:350-414: every WAV of a folder, skipping existing outputs.  The reference loops sequentially; here the

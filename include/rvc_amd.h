@@ -845,6 +845,46 @@ int rvc_mean_abs_diff_workspace_bytes(int64_t rows, int64_t min_t, size_t *bytes
 int rvc_mean_abs_diff_f32(const float *a_dev, int64_t a_stride, const float *b_dev, int64_t b_stride, int64_t rows, int64_t min_t,
                           double *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* ---- K21: the seam of block-by-block conversion, SOLA (csrc/sola.hip) ----------------------------------------------- *
+ * Streaming conversion (rvc_amd/infer/realtime.py) converts a window [carried history | new block] per push and keeps the last
+ * B + X + S samples of the result.  Two consecutive results never line up in phase -- the synthesizer draws fresh noise per call
+ * -- so each one is slid against the tail saved from the previous one to the lag of best normalised correlation and crossfaded
+ * (synchronised overlap-add).  The reference has no such mode: the algorithm below IS the contract, and the yardstick is its
+ * float64 NumPy restatement in tests/sola_ref.py.
+ *
+ * Lengths in output samples: X = xfade, S = search, B = block.  infer[0 .. B + X + S), fp32; buf[0 .. X), fp32, in/out: the tail
+ * the previous call saved, zeros after a reset; fade_in[0 .. X), fp32: the caller's fade, for the stream sin^2(pi i / (2 X))
+ * evaluated in float64 and rounded to fp32.
+ *   1. Score.  For every lag o in 0 .. S inclusive: nom(o) = sum_{i < X} infer[o + i] buf[i], den(o) = sqrt(sum_{i < X}
+ *      infer[o + i]^2 + 1e-8), score(o) = nom(o) / den(o).
+ *   2. offset = the LOWEST o that attains the maximum score.  An all-zero buf scores 0 everywhere and gives offset 0.
+ *   3. out[i] = infer[offset + i] for i < B; for i < X instead out[i] = infer[offset + i] fade_in[i] + buf[i] (1 - fade_in[i]).
+ *   4. buf[i] <- infer[offset + B + i], i < X (read for step 3 before it is overwritten).
+ *   5. *offset_dev = offset (int32, device memory; the library never reads it back).
+ * Arithmetic: fp32.  The two sums of a lag are accumulated per lane over i = lane, lane + 256, ... in index order, the 256 lanes'
+ * sums added by a fixed tree (within a wave of 64 at distances 32, 16, .. 1, then the four waves in order); the quotient and the
+ * square root are correctly rounded; steps 3 and 4 are plain fp32 expressions and copies.  Nothing is accumulated atomically: two
+ * calls give identical bits, on any stream.  A NaN score (a NaN or inf in infer) never wins step 2, which then still yields a lag in
+ * 0 .. S.  Two launches, no synchronisation, no host copy.
+ *
+ * rvc_sola_workspace_bytes: the scratch one call needs, 4 (S + 1) bytes (the scores).  Refused: a NULL bytes; xfade < 1; search
+ *   < 0; either above 2^24.  No device access.
+ * rvc_sola_f32: asynchronous on `hip_stream` (the library's usual trailing `void *stream` argument).  Refused with an error, before
+ *   anything touches the device: a NULL infer_dev, buf_dev, fade_in_dev, out_dev, offset_dev or workspace_dev; xfade < 1; xfade >
+ *   block; search < 0; n_infer above 2^24; n_infer != block + xfade + search; workspace_bytes below the size query's answer;
+ *   out_dev[0 .. B) overlapping infer_dev[0 .. n_infer) or buf_dev[0 .. X); buf_dev overlapping infer_dev.
+ * rvc_stream_window_f32: window_dev[0 .. n_hist + n_block) = [hist_dev | block_dev], then hist_dev <- the last n_hist samples of
+ *   the window (for n_block >= n_hist the end of the block; otherwise the history moves up by n_block).  One launch of one
+ *   workgroup -- the two steps are ordered by its barrier -- sized for a second or two of 16 kHz audio.  n_hist == 0 is allowed
+ *   (the window is the block), and so is n_block == 0; n_hist + n_block == 0 launches nothing.  Refused, before anything touches
+ *   the device: a NULL pointer (also with a length of 0); a negative length; n_hist + n_block above 2^24; window_dev overlapping
+ *   hist_dev[0 .. n_hist) or block_dev[0 .. n_block). */
+int rvc_sola_workspace_bytes(int64_t xfade, int64_t search, size_t *bytes);
+int rvc_sola_f32(const float *infer_dev, int64_t n_infer, float *buf_dev, const float *fade_in_dev, int64_t xfade, int64_t search,
+                 int64_t block, float *out_dev, int *offset_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+int rvc_stream_window_f32(float *hist_dev, int64_t n_hist, const float *block_dev, int64_t n_block, float *window_dev,
+                          void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
