@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes
 import threading
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -200,6 +200,20 @@ SYMBOLS = {
     "rvc_sola_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                              c_void_p]),
     "rvc_stream_window_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rvc_fx_pointwise_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "rvc_fx_delay_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "rvc_fx_chorus_workspace_bytes": (c_int, [c_int64, c_double, POINTER(c_size_t)]),
+    "rvc_fx_chorus_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "rvc_fx_reverb_params": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "rvc_fx_reverb_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "rvc_fx_reverb_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    "rvc_fx_ballistics": (c_int, [c_int, c_double, c_double, POINTER(c_double), POINTER(c_double)]),
+    "rvc_fx_compressor_workspace_bytes": (c_int, [c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "rvc_fx_compressor_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_double, c_int64, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "rvc_fx_limiter_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -718,6 +732,91 @@ def sola(infer: torch.Tensor, buf: torch.Tensor, fade_in: torch.Tensor, search: 
     _call("rvc_sola_f32", dev, infer.data_ptr(), infer.numel(), buf.data_ptr(), fade_in.data_ptr(), xfade, search, block,
           out.data_ptr(), offset.data_ptr(), ws.data_ptr(), ws.numel())
     return out, offset
+
+
+# ---- K22 -----------------------------------------------------------------------------------------
+FX_GAIN, FX_DISTORTION, FX_BITCRUSH, FX_CLIPPING = 1, 2, 4, 8
+
+
+def fx_reverb_params(sr: int):
+    """-> (comb lengths [8], allpass lengths [4]) of rvc_fx_reverb_f32 at `sr`.  No device access."""
+    comb, allpass = (c_int * 8)(), (c_int * 4)()
+    _check(_lib.rvc_fx_reverb_params(int(sr), comb, allpass), "rvc_fx_reverb_params")
+    return list(comb), list(allpass)
+
+
+def fx_ballistics(sr: int, attack_ms: float, release_ms: float):
+    """-> (c_attack, c_release) as rvc_fx_compressor_f32 derives them, in double.  No device access."""
+    ca, cr = c_double(), c_double()
+    _check(_lib.rvc_fx_ballistics(int(sr), float(attack_ms), float(release_ms), ctypes.byref(ca), ctypes.byref(cr)), "rvc_fx_ballistics")
+    return ca.value, cr.value
+
+
+def _fx_signal(x, what: str) -> torch.Tensor:
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise NativeError(f"{what} wants a 1-D float32 HBM tensor")
+    return _dev_f32(x, "x")
+
+
+def fx_pointwise(x: torch.Tensor, stages: int, gain_db: float = 0.0, drive_db: float = 0.0, bit_depth: float = 8.0,
+                 clip_threshold_db: float = 0.0) -> torch.Tensor:
+    """rvc_fx_pointwise_f32 (K22): the enabled stages of gain | distortion | bitcrush | clipping, in that order, in one launch."""
+    x = _fx_signal(x, "fx_pointwise")
+    out = torch.empty_like(x)
+    _call("rvc_fx_pointwise_f32", x.device, x.data_ptr() or 1, x.numel(), int(stages), float(gain_db), float(drive_db), float(bit_depth),
+          float(clip_threshold_db), out.data_ptr() or 1)   # an empty tensor has no storage: n == 0 touches nothing
+    return out
+
+
+def fx_delay(x: torch.Tensor, sr: int, delay_seconds: float, feedback: float, mix: float) -> torch.Tensor:
+    """rvc_fx_delay_f32 (K22): one launch on the device's current stream."""
+    x = _fx_signal(x, "fx_delay")
+    out = torch.empty_like(x)
+    _call("rvc_fx_delay_f32", x.device, x.data_ptr() or 1, x.numel(), int(sr), float(delay_seconds), float(feedback), float(mix),
+          out.data_ptr() or 1)
+    return out
+
+
+def fx_chorus(x: torch.Tensor, sr: int, rate_hz: float, depth: float, centre_delay_ms: float, feedback: float, mix: float) -> torch.Tensor:
+    """rvc_fx_chorus_f32 (K22): a gather for feedback 0, otherwise one workgroup walking the signal (slow)."""
+    x = _fx_signal(x, "fx_chorus")
+    out = torch.empty_like(x)
+    ws = _workspace("fx_chorus", x.device, "rvc_fx_chorus_workspace_bytes", x.numel(), float(feedback))
+    _call("rvc_fx_chorus_f32", x.device, x.data_ptr() or 1, x.numel(), int(sr), float(rate_hz), float(depth), float(centre_delay_ms),
+          float(feedback), float(mix), out.data_ptr() or 1, ws.data_ptr(), ws.numel())
+    return out
+
+
+def fx_reverb(x: torch.Tensor, sr: int, room_size: float, damping: float, wet_level: float, dry_level: float, width: float,
+              freeze_mode: float) -> torch.Tensor:
+    """rvc_fx_reverb_f32 (K22): Freeverb's mono path, seven launches."""
+    x = _fx_signal(x, "fx_reverb")
+    out = torch.empty_like(x)
+    ws = _workspace("fx_reverb", x.device, "rvc_fx_reverb_workspace_bytes", x.numel())
+    _call("rvc_fx_reverb_f32", x.device, x.data_ptr() or 1, x.numel(), int(sr), float(room_size), float(damping), float(wet_level),
+          float(dry_level), float(width), float(freeze_mode), out.data_ptr() or 1, ws.data_ptr(), ws.numel())
+    return out
+
+
+def fx_compressor(x: torch.Tensor, sr: int, threshold_db: float, ratio: float, attack_ms: float, release_ms: float,
+                  chunk: int = 0) -> torch.Tensor:
+    """rvc_fx_compressor_f32 (K22); `chunk` = 0 lets the library choose (the result does not depend on it)."""
+    x = _fx_signal(x, "fx_compressor")
+    out = torch.empty_like(x)
+    ws = _workspace("fx_compressor", x.device, "rvc_fx_compressor_workspace_bytes", x.numel(), int(chunk), 0)
+    _call("rvc_fx_compressor_f32", x.device, x.data_ptr() or 1, x.numel(), int(sr), float(threshold_db), float(ratio), float(attack_ms),
+          float(release_ms), int(chunk), out.data_ptr() or 1, ws.data_ptr(), ws.numel())
+    return out
+
+
+def fx_limiter(x: torch.Tensor, sr: int, threshold_db: float, release_ms: float, chunk: int = 0) -> torch.Tensor:
+    """rvc_fx_limiter_f32 (K22): two compressors, the make-up gain and the clamp."""
+    x = _fx_signal(x, "fx_limiter")
+    out = torch.empty_like(x)
+    ws = _workspace("fx_limiter", x.device, "rvc_fx_compressor_workspace_bytes", x.numel(), int(chunk), 1)
+    _call("rvc_fx_limiter_f32", x.device, x.data_ptr() or 1, x.numel(), int(sr), float(threshold_db), float(release_ms), int(chunk),
+          out.data_ptr() or 1, ws.data_ptr(), ws.numel())
+    return out
 
 
 # ---- K5 ------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """``VoiceConverter`` -- orchestration around the pipeline with the reference's surface
-(rvc/infer/infer.py:41-493).  File decoding/resampling and the pedalboard effects are out of
-scope; ``clean_audio`` runs the native spectral gate (rvc_amd.lib.noise_reduce, K18) and
-``formant_shifting`` the native formant shifter (rvc_amd.lib.formant_shift, K19).
+(rvc/infer/infer.py:41-493).  File decoding/resampling is out of
+scope; ``clean_audio`` runs the native spectral gate (rvc_amd.lib.noise_reduce, K18),
+``formant_shifting`` the native formant shifter (rvc_amd.lib.formant_shift, K19) and ``convert_array(post_process=True, ...)``
+the native effects board (rvc_amd.lib.effects, K22; ``convert_audio`` itself still refuses post_process).
 ``convert_audio`` reads WAV files of any rate / channel count / PCM or float encoding
 (rvc_amd.lib.audio: own RIFF parser, device-side polyphase resampler to 16 kHz in place of soxr) and writes 16-bit WAV, or
 use ``convert_array`` with a NumPy signal.  ``open_stream`` converts block by block (rvc_amd.infer.realtime, K21; not in the reference).
@@ -19,6 +20,8 @@ import torch
 from rvc_amd.configs.config import Config
 from rvc_amd.infer.pipeline import Pipeline as VC
 from rvc_amd.lib.audio import load_audio_infer
+from rvc_amd.lib.effects import (Bitcrush, Chorus, Clipping, Compressor, Delay, Distortion, Gain, Limiter, Pedalboard, PitchShift,
+                                 Reverb)
 from rvc_amd.lib.formant_shift import shift_formants
 from rvc_amd.lib.algorithm.synthesizers import Synthesizer
 from rvc_amd.lib.hubert import HubertModelWithFinalProj
@@ -126,16 +129,54 @@ class VoiceConverter:
             print(f"An error occurred removing audio noise: {error}")
             return None
 
+    # ---- effects (infer.py:130-191) ----
+    # the chain in the reference's order: (switch, effect, {the effect's argument: (keyword, default)})
+    EFFECT_CHAIN = (
+        ("reverb", Reverb, dict(room_size=("reverb_room_size", 0.5), damping=("reverb_damping", 0.5), wet_level=("reverb_wet_level", 0.33),
+                                dry_level=("reverb_dry_level", 0.4), width=("reverb_width", 1.0), freeze_mode=("reverb_freeze_mode", 0))),
+        ("pitch_shift", PitchShift, dict(semitones=("pitch_shift_semitones", 0))),
+        ("limiter", Limiter, dict(threshold_db=("limiter_threshold", -6), release_ms=("limiter_release", 0.05))),
+        ("gain", Gain, dict(gain_db=("gain_db", 0))),
+        ("distortion", Distortion, dict(drive_db=("distortion_gain", 25))),
+        ("chorus", Chorus, dict(rate_hz=("chorus_rate", 1.0), depth=("chorus_depth", 0.25), centre_delay_ms=("chorus_delay", 7),
+                                feedback=("chorus_feedback", 0.0), mix=("chorus_mix", 0.5))),
+        ("bitcrush", Bitcrush, dict(bit_depth=("bitcrush_bit_depth", 8))),
+        ("clipping", Clipping, dict(threshold_db=("clipping_threshold", 0))),
+        ("compressor", Compressor, dict(threshold_db=("compressor_threshold", 0), ratio=("compressor_ratio", 1),
+                                        attack_ms=("compressor_attack", 1.0), release_ms=("compressor_release", 100))),
+        ("delay", Delay, dict(delay_seconds=("delay_seconds", 0.5), feedback=("delay_feedback", 0.0), mix=("delay_mix", 0.5))),
+    )
+    EFFECT_KEYWORDS = frozenset(k for switch, _, args in EFFECT_CHAIN for k in (switch, *(kw for kw, _ in args.values())))
+
+    @staticmethod
+    def post_process_audio(audio_input, sample_rate, **kwargs):
+        """The reference's effects chain, in its order, on the native board (K22): a NumPy array or a device tensor, same kind out.
+        An effect runs when its switch (reverb=True, ...) is set; a parameter that is not given takes the reference's default.
+        pitch_shift raises NotImplementedError (rvc_amd.lib.effects.PitchShift)."""
+        board = Pedalboard()
+        for switch, effect, args in VoiceConverter.EFFECT_CHAIN:
+            if kwargs.get(switch, False):
+                board.append(effect(**{name: kwargs.get(keyword, default) for name, (keyword, default) in args.items()}))
+        return board(audio_input, sample_rate)
+
     # ---- conversion ----
     def convert_array(self, audio: np.ndarray, *, index_path: str = "", pitch: int = 0, f0_file=None,
                       f0_method: str = "rmvpe", index_rate: float = 0.75, volume_envelope: float = 1,
                       protect: float = 0.5, hop_length: int = 128, f0_autotune: bool = False,
                       f0_autotune_strength: float = 1, filter_radius: float = 3.0, sid: int = 0, noise_seed=None,
                       split_audio: bool = False, clean_audio: bool = False, clean_strength: float = 0.5,
-                      formant_shifting: bool = False, formant_qfrency: float = 0.8, formant_timbre: float = 0.8):
+                      formant_shifting: bool = False, formant_qfrency: float = 0.8, formant_timbre: float = 0.8,
+                      post_process: bool = False, **effects):
         """The array-level core of convert_audio (infer.py:262-325): 16 kHz float array in, float32 @tgt_sr out; clean_audio runs
         remove_audio_noise over the result on the same stream and keeps the uncleaned audio when that fails; formant_shifting runs
-        shift_formants (K19) over the input on the same stream BEFORE the peak limiting, where load_audio_infer has it."""
+        shift_formants (K19) over the input on the same stream BEFORE the peak limiting, where load_audio_infer has it;
+        post_process runs post_process_audio (K22) with the effect keywords (EFFECT_KEYWORDS: reverb=True, reverb_room_size=...,
+        as convert_audio's **kwargs name them) at tgt_sr after clean_audio, on the same stream."""
+        for name in effects:
+            if name not in self.EFFECT_KEYWORDS:
+                raise TypeError(f"convert_array() got an unexpected keyword argument '{name}'")
+        if post_process and effects.get("pitch_shift", False):
+            raise NotImplementedError("pitch_shift is not part of this build (rvc_amd.lib.effects.PitchShift)")
         if formant_shifting:        # utils.py:70-82
             audio = audio.to(device=self.config.device, dtype=torch.float64) if torch.is_tensor(audio) else np.asarray(audio, dtype=np.float64)
             audio = shift_formants(audio, 16000, formant_qfrency, formant_timbre, device=self.config.device)
@@ -162,7 +203,8 @@ class VoiceConverter:
 
         def done(out):   # infer.py:320-325
             cleaned = self.remove_audio_noise(out, self.tgt_sr, clean_strength) if clean_audio else None
-            return out if cleaned is None else cleaned
+            out = out if cleaned is None else cleaned
+            return self.post_process_audio(out, self.tgt_sr, **effects) if post_process else out
 
         if not split_audio:
             return done(run(audio))
@@ -185,7 +227,8 @@ class VoiceConverter:
         small launches -- so interleaved utterances finish sooner than in sequence: 30.4 / 26.0 / 25.1-25.7 ms per 30 s
         utterance at 1 / 2 / 3 in flight (round 6, profiles/r06_inflight_sweep.txt; each one in flight keeps ~2.5 GB of workspaces).  Results keep the input
         order; device tensors in give device tensors out (valid once this returns).  The keywords are convert_array's:
-        formant_shifting / formant_qfrency / formant_timbre and clean_audio / clean_strength run on the utterance's own stream."""
+        formant_shifting / formant_qfrency / formant_timbre, clean_audio / clean_strength and post_process with its effect
+        keywords run on the utterance's own stream."""
         import threading
         audios = list(audios)
         results = [None] * len(audios)

@@ -885,6 +885,77 @@ int rvc_sola_f32(const float *infer_dev, int64_t n_infer, float *buf_dev, const 
 int rvc_stream_window_f32(float *hist_dev, int64_t n_hist, const float *block_dev, int64_t n_block, float *window_dev,
                           void *hip_stream);
 
+/* ---- K22: post_process, the effects board (csrc/effects.hip) -------------------------------------------------------- *
+ * Replaces the `pedalboard` chain of post_process_audio (rvc/infer/infer.py:130-191) on the converted waveform.  The pedalboard
+ * wheel (JUCE underneath) is absent: the formulas below were written down from memory of JUCE / pedalboard and could not be
+ * checked against either, so parity with the wheel is unpinned -- the algorithm below IS the contract, and the yardstick is its
+ * float64 NumPy restatement in tests/effects_ref.py.  Parameters are constant over the signal: JUCE's 50 ms parameter smoothing
+ * is NOT modelled.  PitchShift (Rubber Band) is not built and has no entry point.
+ *
+ * Every call: mono fp32 x[n] -> fp32 out[n] (tails are cut at n), asynchronous on `hip_stream`.  dB values become linear factors
+ * as 10^(dB / 20) in double on the host and are rounded to fp32 once; so are 1 - mix, 1 - damp and the other derived constants.
+ *   pointwise   `stages` is a set of gain 1 | distortion 2 | bitcrush 4 | clipping 8; the enabled ones run in that order in one
+ *               pass.  gain: y = x g, g = 10^(gain_db / 20).  distortion: y = tanh(x 10^(drive_db / 20)).  bitcrush: y = rint(x 2^b)
+ *               / 2^b, round-half-even, 0 < b <= 32.  clipping: y = clamp(x, -t, t), t = 10^(clip_threshold_db / 20).
+ *   delay       D = floor(delay_seconds sr), D >= 1.  d[m] = x[m - D] + fb d[m - D] (0 for m < D); y[m] = (1 - mix) x[m] + mix d[m].
+ *   chorus      per sample m, in float64: ph = frac(rate_hz m / sr), lfo = sin(2 pi ph), ms = max(1, centre_delay_ms + (10 depth)
+ *               lfo), dl = ms sr / 1000, i = floor(dl), f = dl - i (then fp32).  p[m] = x[m] - fb w[m - 1]; w[m] = p[m - i] + f
+ *               (p[m - i - 1] - p[m - i]) with p[< 0] = 0, w[-1] = 0; y[m] = (1 - mix) x[m] + mix w[m].
+ *   reverb      Freeverb, mono path.  in = 0.015 x, or 0 when freeze_mode >= 0.5.  Eight parallel combs of length (sr T) / 44100
+ *               (integer division), T = 1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617, each: o = line[idx]; last = o (1 - damp) +
+ *               last damp; line[idx] = in + last feedback.  Their outputs added in that order go through four series allpasses, T =
+ *               556, 441, 341, 225, each: b = line[idx]; line[idx] = in + 0.5 b; out = b - in.  y = out wet1 + x dry.  damp = 0.4
+ *               damping, feedback = 0.28 room_size + 0.7 (frozen: damp = 0, feedback = 1); wet1 = 1.5 wet_level (1 + width), dry =
+ *               2 dry_level.
+ *   compressor  e[m] = a + c (e[m - 1] - a), a = |x[m]|, e[-1] = 0, c = c_attack if a > e[m - 1] else c_release; c_* =
+ *               exp(-2 pi 1000 / (sr t_ms)) for t_ms = attack_ms / release_ms, and 0 when t_ms <= 1e-3.  gain = 1 if e < thr else
+ *               (e / thr)^(1 / ratio - 1), thr = 10^(threshold_db / 20); y = gain x.
+ *   limiter     compressor(-10 dB, ratio 4, attack 2 ms, release 200 ms), then compressor(threshold_db, ratio 1000, attack
+ *               0.001 ms (c_attack = 0), release_ms), then times 10^(7.5 / 40) 10^(-threshold_db / 20), then clamp to [-1, 1].
+ * Arithmetic: fp32 (subnormals kept), a x + b as one fused multiply-add where the formula has that shape; the chorus tap position
+ * float64.  Where the state lives: the delay and the allpasses keep their line in a register (one lane per residue class mod the
+ * line's length: no line exists in memory); a comb's line is its output row in the workspace and its damping filter is scanned
+ * over chunks of the comb's length by one workgroup; the chorus with feedback keeps p[] in the workspace and walks blocks of the
+ * shortest tap delay in ONE workgroup (slow: n / block steps; feedback 0 is a plain gather); the compressor runs chunks of the
+ * signal from the two entry states 0 and max|x| -- every step is a monotone map of the state, in floating point too, so a chunk
+ * whose two end states are bit-identical has THE end state -- then chains the chunks that did not close and runs every chunk from
+ * its exact entry state.  Its output is the sequential recurrence's bit for bit and does not depend on `chunk` (0: the library
+ * chooses ceil(28 / -ln max(c_attack, c_release)), at least 256).  A release so long that no chunk closes degrades to one lane
+ * walking the signal: correct, and slow.  No atomics except a maximum: two calls give identical bits.
+ *
+ * Accepted: 0 <= n <= 2^27 (n == 0 succeeds and touches nothing); 8000 <= sr <= 96000.  Refused with an error that names the
+ * argument, before anything touches the device: a NULL pointer; n or sr outside that; any dB value outside [-200, 200]; stages
+ * outside 1 .. 15 (only the enabled stages' parameters are looked at); bit_depth outside (0, 32]; delay_seconds outside [0, 60] or
+ * shorter than one sample; feedback outside [-1, 1]; mix outside [0, 1]; rate_hz outside [0, 100]; depth outside [0, 10];
+ * centre_delay_ms, or centre_delay_ms + 10 depth, outside [0, 100]; room_size, damping, wet_level, dry_level, width, freeze_mode
+ * outside [0, 1]; ratio outside [1, 1e6]; attack_ms, release_ms outside [0, 1e6]; chunk < 0; limiter neither 0 nor 1; NaN
+ * anywhere; workspace_bytes below the size query's answer; out_dev overlapping x_dev (pointwise alone allows out_dev == x_dev);
+ * the workspace overlapping either.
+ *
+ * rvc_fx_reverb_params: the eight comb and four allpass lengths at sr (host only).  rvc_fx_ballistics: c_attack and c_release in
+ *   double, as the compressor derives them before rounding to fp32 (host only).
+ * rvc_fx_chorus_workspace_bytes: 0 for feedback == 0 (workspace_dev may then be NULL), else 12 n.  rvc_fx_reverb_workspace_bytes:
+ *   36 n.  rvc_fx_compressor_workspace_bytes: 16 + 12 ceil(n / chunk) rounded up to 16 (chunk 0 counts as 256), plus 4 n for the
+ *   limiter (`limiter` = 1). */
+int rvc_fx_pointwise_f32(const float *x_dev, int64_t n, int stages, double gain_db, double drive_db, double bit_depth,
+                         double clip_threshold_db, float *out_dev, void *hip_stream);
+int rvc_fx_delay_f32(const float *x_dev, int64_t n, int sr, double delay_seconds, double feedback, double mix, float *out_dev,
+                     void *hip_stream);
+int rvc_fx_chorus_workspace_bytes(int64_t n, double feedback, size_t *bytes);
+int rvc_fx_chorus_f32(const float *x_dev, int64_t n, int sr, double rate_hz, double depth, double centre_delay_ms, double feedback,
+                      double mix, float *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+int rvc_fx_reverb_params(int sr, int *comb_len, int *allpass_len);
+int rvc_fx_reverb_workspace_bytes(int64_t n, size_t *bytes);
+int rvc_fx_reverb_f32(const float *x_dev, int64_t n, int sr, double room_size, double damping, double wet_level, double dry_level,
+                      double width, double freeze_mode, float *out_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+int rvc_fx_ballistics(int sr, double attack_ms, double release_ms, double *c_attack, double *c_release);
+int rvc_fx_compressor_workspace_bytes(int64_t n, int64_t chunk, int limiter, size_t *bytes);
+int rvc_fx_compressor_f32(const float *x_dev, int64_t n, int sr, double threshold_db, double ratio, double attack_ms,
+                          double release_ms, int64_t chunk, float *out_dev, void *workspace_dev, size_t workspace_bytes,
+                          void *hip_stream);
+int rvc_fx_limiter_f32(const float *x_dev, int64_t n, int sr, double threshold_db, double release_ms, int64_t chunk, float *out_dev,
+                       void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
