@@ -214,6 +214,9 @@ SYMBOLS = {
     "rvc_fx_compressor_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_double, c_int64, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
     "rvc_fx_limiter_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_spectral_features_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "rvc_spectral_features_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_size_t, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -689,6 +692,25 @@ def formant_shift(x: torch.Tensor, sr: int, quefrency_s: float, distortion: floa
     _call("rvc_formant_shift_f32", x.device, x.data_ptr(), n, int(sr), float(quefrency_s), float(distortion), int(group_frames),
           out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
+
+
+# ---- K23 -----------------------------------------------------------------------------------------
+def spectral_features(x: torch.Tensor, sr: int, roll_percent: float = 0.85, want_mag: bool = False, want_db: bool = False):
+    """The analyzer's spectral features of include/rvc_amd.h (K23) over x: 1-D float32 on the device -> (cent, bw, rolloff, mag,
+    db) on the same device, enqueued on its current stream.  The curves are float64 [F], F = 1 + n // 512; mag and db are
+    float32 [F, 1025] (frame-major), or None where not asked for: a plane that is not wanted is never written."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise NativeError("spectral_features wants a 1-D float32 HBM tensor")
+    x = _dev_f32(x, "x")
+    n = x.numel()
+    ws = _workspace("spectral_features", x.device, "rvc_spectral_features_workspace_bytes", n)
+    frames = 1 + n // 512
+    curves = torch.empty(3, frames, dtype=torch.float64, device=x.device)
+    mag = torch.empty(frames, 1025, dtype=torch.float32, device=x.device) if want_mag else None
+    db = torch.empty(frames, 1025, dtype=torch.float32, device=x.device) if want_db else None
+    _call("rvc_spectral_features_f32", x.device, x.data_ptr(), n, int(sr), float(roll_percent), _ptr(mag), _ptr(db),
+          curves[0].data_ptr(), curves[1].data_ptr(), curves[2].data_ptr(), ws.data_ptr(), ws.numel())
+    return curves[0], curves[1], curves[2], mag, db
 
 
 # ---- K21 -----------------------------------------------------------------------------------------

@@ -956,6 +956,48 @@ int rvc_fx_compressor_f32(const float *x_dev, int64_t n, int sr, double threshol
 int rvc_fx_limiter_f32(const float *x_dev, int64_t n, int sr, double threshold_db, double release_ms, int64_t chunk, float *out_dev,
                        void *workspace_dev, size_t workspace_bytes, void *hip_stream);
 
+/* ---- K23: the audio analyzer's spectral features (csrc/specfeat.hip) -------------------------------------------------- *
+ * What calculate_features of the reference's audio analyzer (rvc/lib/tools/analyzer.py) takes from librosa 0.11 with the defaults
+ * its calls use: stft -> |S|, spectral_centroid, spectral_bandwidth, spectral_rolloff, and amplitude_to_db(|S|, ref = np.max) for
+ * the figure.  librosa absent: parity with the wheel unpinned -- the algorithm below IS the contract, and the yardstick is its
+ * float64 scipy.fft restatement in tests/spectral_features_ref.py.
+ *
+ * x: fp32 [n] at `sr`.  N = 2048, H = 512, B = 1025.
+ *   1. Frames.  center = True with pad_mode = "constant": x is extended by 1024 zeros on each side; F = 1 + n / 512 frames (integer
+ *      division); frame t is xpad[t H .. t H + N) times the periodic Hann window w[i] = 0.5 - 0.5 cos(2 pi i / N); S[t][k] = the
+ *      unscaled rDFT, k < B; m = |S| (fp32).
+ *   2. Per frame, in float64 over the fp32 magnitudes, with f_k = k sr / N: s0 = sum m; mn = m / s0, or m / 1 when s0 is below the
+ *      smallest normal float32 (normalize(norm = 1) and its `tiny` threshold); centroid c = sum f_k mn_k; bandwidth =
+ *      sqrt(sum mn_k (f_k - c)^2) (p = 2, norm = True); roll-off = f_j for the first j whose cumulative sum m_0 + .. + m_j is at
+ *      least roll_percent s0.  A frame of digital silence gives 0, 0 and 0 Hz, never NaN.
+ *   3. dB plane (optional): R = the maximum of m over the whole signal; db = 10 log10(max(1e-10, m^2)) - 10 log10(max(1e-10, R^2)),
+ *      then max(db, max(db) - 80).  An all-silent signal gives 0 everywhere.
+ *   4. cent, bw, rolloff: float64 [F].  mag and db: fp32 [F][B], frame-major, each optional: a NULL pointer skips that plane, and
+ *      with both NULL no spectrogram reaches HBM at all.
+ * Arithmetic: the DFT is a GEMM on the exact-fp32 matrix cores: a dot product is summed as fmaf chains in sample order over
+ * consecutive ranges of 64 samples whose sums are added in range order; the window (fp32 roundings of float64 values) multiplies
+ * the sample in fp32; cosines and sines are fp32 roundings of float64 values looked up at (sample index * k) mod 2048.  The Nyquist
+ * bin is computed as sum (-1)^i of the windowed frame.  |S| is formed in FLOAT64 from the fp32 real and imaginary parts
+ * (sqrt(re^2 + im^2), the squares exact) and rounded to fp32 once.  A workgroup owns 32 frames and all their bins and keeps the
+ * magnitudes in LDS; the sums of step 2 are float64, partial per range of 64 consecutive bins (the last range holds bin 1024 too)
+ * and merged in bin order.  The bandwidth is the TWO-PASS form: the centroid is merged first, then sum mn_k (f_k - c)^2 runs over the
+ * magnitudes held in LDS -- no difference of moments.  The roll-off scan of a range starts from the merged sum of the ranges
+ * before it.  The dB plane is float64 per element (log10) and rounded to fp32; its maximum is found in a first pass (per-workgroup
+ * maxima of m, merged per group of launches) and applied in a second, in place.  Nothing is accumulated atomically and a maximum
+ * does not depend on order: two calls give identical bits, on any stream, with or without either plane.
+ *
+ * rvc_spectral_features_workspace_bytes: the scratch one call needs: 256 bytes + 4 per workgroup of one launch group (ceil(F / 32)
+ *   workgroups, at most 128 = 4096 frames: a longer signal is walked group by group and needs no more), rounded up to 256.  No device access;
+ *   refuses n < 1 and n above 2^27.
+ * rvc_spectral_features_f32: asynchronous on `hip_stream` (the library's usual trailing `void *stream` argument).  Refused with an
+ *   error, before anything touches the device: a NULL x_dev, cent_dev, bw_dev, rolloff_dev or workspace_dev; a signal, plane or
+ *   workspace not 4-byte aligned, a curve not 8-byte aligned; n < 1 or n > 2^27; sr < 1; roll_percent not finite or outside the
+ *   open interval (0, 1); db_dev == mag_dev when both are non-NULL; workspace_bytes below the size query's answer. */
+int rvc_spectral_features_workspace_bytes(int64_t n, size_t *bytes);
+int rvc_spectral_features_f32(const float *x_dev, int64_t n, int sr, double roll_percent, float *mag_dev, float *db_dev,
+                              double *cent_dev, double *bw_dev, double *rolloff_dev, void *workspace_dev, size_t workspace_bytes,
+                              void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
