@@ -217,6 +217,12 @@ SYMBOLS = {
     "rvc_spectral_features_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
     "rvc_spectral_features_f32": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_size_t, c_void_p]),
+    "rvc_melcep_workspace_bytes": (c_int, [c_int64, c_int, POINTER(c_size_t)]),
+    "rvc_melcep_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_dtw_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "rvc_dtw_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_frame_dist_sum_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "rvc_f0_track_sums_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 for _name, (_res, _args) in SYMBOLS.items():
@@ -711,6 +717,68 @@ def spectral_features(x: torch.Tensor, sr: int, roll_percent: float = 0.85, want
     _call("rvc_spectral_features_f32", x.device, x.data_ptr(), n, int(sr), float(roll_percent), _ptr(mag), _ptr(db),
           curves[0].data_ptr(), curves[1].data_ptr(), curves[2].data_ptr(), ws.data_ptr(), ws.numel())
     return curves[0], curves[1], curves[2], mag, db
+
+
+# ---- K24 -----------------------------------------------------------------------------------------
+def melcep(x: torch.Tensor, sr: int, mel: torch.Tensor, n_coef: int) -> torch.Tensor:
+    """rvc_melcep_f32 (K24): x 1-D float32 on the device at `sr`, mel float32 [n_mels, 513] on the same device -> the mel-cepstral
+    coefficients c[1 .. n_coef] per 5 ms frame, float32 [1 + n // (sr // 200), n_coef]."""
+    if not torch.is_tensor(x) or x.dim() != 1:
+        raise NativeError("melcep wants a 1-D float32 HBM tensor")
+    if not torch.is_tensor(mel) or mel.dim() != 2 or mel.shape[1] != 513:
+        raise NativeError("melcep wants the mel filterbank as a float32 [n_mels, 513] HBM tensor")
+    _device(x, mel)
+    x, mel = _dev_f32(x, "x"), _dev_f32(mel, "mel")
+    n, sr = x.numel(), int(sr)
+    ws = _workspace("melcep", x.device, "rvc_melcep_workspace_bytes", n, sr)     # refuses n < 1 and a rate outside the rule
+    out = torch.empty(1 + n // (sr // 200), int(n_coef), dtype=torch.float32, device=x.device)
+    _call("rvc_melcep_f32", x.device, x.data_ptr(), n, sr, mel.data_ptr(), mel.shape[0], int(n_coef), out.data_ptr(), ws.data_ptr(),
+          ws.numel())
+    return out
+
+
+def _features_pair(a: torch.Tensor, b: torch.Tensor, what: str):
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise NativeError(f"{what} wants two [frames, dim] float32 HBM tensors of one dim")
+    _device(a, b)
+    return _dev_f32(a, f"{what}: a"), _dev_f32(b, f"{what}: b")
+
+
+def dtw(a: torch.Tensor, b: torch.Tensor, band: int = -1):
+    """rvc_dtw_f64 (K24) -> (out, path) on the device: out float64 [2] = (the total cost, the path's length L), path int32
+    [Ta + Tb - 1, 2] of which the first L rows are written.  band < 0: no band."""
+    a, b = _features_pair(a, b, "dtw")
+    ta, tb = a.shape[0], b.shape[0]
+    ws = _workspace("dtw", a.device, "rvc_dtw_workspace_bytes", ta, tb)
+    out = torch.empty(2, dtype=torch.float64, device=a.device)
+    path = torch.empty(ta + tb - 1, 2, dtype=torch.int32, device=a.device)
+    _call("rvc_dtw_f64", a.device, a.data_ptr(), ta, b.data_ptr(), tb, a.shape[1], int(band), out.data_ptr(), path.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return out, path
+
+
+def frame_dist_sum(a: torch.Tensor, b: torch.Tensor, frames: int) -> torch.Tensor:
+    """rvc_frame_dist_sum_f64 (K24): the sum of the Euclidean distances of the first `frames` rows of a and b -> float64 [1]."""
+    a, b = _features_pair(a, b, "frame_dist_sum")
+    if frames > min(a.shape[0], b.shape[0]):
+        raise NativeError(f"frame_dist_sum: frames = {frames} exceeds a length ({a.shape[0]}, {b.shape[0]})")
+    out = torch.empty(1, dtype=torch.float64, device=a.device)
+    _call("rvc_frame_dist_sum_f64", a.device, a.data_ptr(), b.data_ptr(), int(frames), a.shape[1], out.data_ptr())
+    return out
+
+
+def f0_track_sums(f0_a: torch.Tensor, f0_b: torch.Tensor) -> torch.Tensor:
+    """rvc_f0_track_sums_f64 (K24): two 1-D float64 contours of equal length on the device -> the twelve sums of include/rvc_amd.h,
+    float64 [12]."""
+    if not (torch.is_tensor(f0_a) and torch.is_tensor(f0_b)) or f0_a.dim() != 1 or f0_a.shape != f0_b.shape:
+        raise NativeError("f0_track_sums wants two 1-D float64 HBM tensors of equal length")
+    device = _device(f0_a, f0_b)
+    if not f0_a.is_cuda or f0_a.dtype != torch.float64 or f0_b.dtype != torch.float64:
+        raise NativeError("f0_track_sums wants float64 contours in HBM (no CPU fallback)")
+    f0_a, f0_b = f0_a.contiguous(), f0_b.contiguous()
+    out = torch.empty(12, dtype=torch.float64, device=device)
+    _call("rvc_f0_track_sums_f64", device, f0_a.data_ptr(), f0_b.data_ptr(), f0_a.numel(), out.data_ptr())
+    return out
 
 
 # ---- K21 -----------------------------------------------------------------------------------------

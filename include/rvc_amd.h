@@ -998,6 +998,60 @@ int rvc_spectral_features_f32(const float *x_dev, int64_t n, int sr, double roll
                               double *cent_dev, double *bw_dev, double *rolloff_dev, void *workspace_dev, size_t workspace_bytes,
                               void *hip_stream);
 
+/* ---- K24: the conversion scorer (csrc/convscore.hip) ------------------------------------------------------------------ *
+ * How good is a conversion: the mel-cepstral distortion against a parallel target after dynamic time warping, and the F0 tracking
+ * errors between the input and the converted output.  The reference has no such tool and no third-party MCD package was
+ * available: the algorithm below IS the contract, and the yardstick is its float64 NumPy restatement in
+ * tests/conversion_score_ref.py.  Parity with any MCD package is unpinned.
+ *
+ * rvc_melcep_f32: x fp32 [n] at `sr` (a multiple of 200 in 8000 .. 48000) -> c fp32 [T][n_coef].
+ *   1. hop = sr / 200 (5 ms); T = 1 + n / hop (integer division); frame t is samples [t hop - 512, t hop + 512) of x extended with
+ *      zeros, times the periodic Hann window w[i] = 0.5 - 0.5 cos(2 pi i / 1024); S[t][k] = the unscaled rDFT, k <= 512.
+ *   2. P[k] = re^2 + im^2;  M[m] = sum_k W[m][k] P[k] with W = mel_dev, fp32 [n_mels][513], row-major (the caller's filterbank);
+ *      L[m] = 0.5 ln(max(M[m], 1e-10));  c[k] = (1 / n_mels) sum_m L[m] cos(pi k (2 m + 1) / (2 n_mels)), k = 1 .. n_coef (c[0], the
+ *      energy term, is left out).
+ *   Arithmetic: the DFT is the GEMM of K18 / K19 on the exact-fp32 matrix cores (window times sample in fp32; a dot product summed as
+ *   16 fmaf chains of 64 samples added in order).  Everything after it is FLOAT64: P from the fp32 re and im; M as 64 interleaved
+ *   partial sums (bins k = lane mod 64) merged by a fixed pairwise tree; the log; the DCT summed in order of m with the cosine
+ *   argument reduced exactly; one rounding to fp32 at the end.  The power spectrum goes through the workspace, a group of at most
+ *   2048 frames at a time, so the scratch does not grow with the signal.  Digital silence gives c = 0 exactly up to the DCT's own
+ *   rounding (every L[m] is 0.5 ln 1e-10).  Two calls give identical bits.
+ *   Refused: a NULL or misaligned pointer; n < 1 or n > 2^27; sr outside the rule; n_coef outside 1 .. 40; n_mels outside
+ *   n_coef + 1 .. 128; workspace_bytes below rvc_melcep_workspace_bytes(n, sr) (= 8704 bytes per frame of one group rounded up to
+ *   128 frames: 17 MiB from 2048 frames on).
+ *
+ * rvc_dtw_f64: a fp32 [Ta][dim], b fp32 [Tb][dim], 1 <= Ta, Tb <= 16384, 1 <= dim <= 64.
+ *   d(i, j) = sqrt(sum_q (a[i][q] - b[j][q])^2) in float64, the terms added in the order q = 0 .. dim - 1 (fused multiply-add).
+ *   D(0, 0) = d(0, 0); otherwise D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)) in float64; the predecessors are tried in
+ *   that order and a later one replaces the best only when STRICTLY smaller; a predecessor outside the lattice counts as +inf.
+ *   band < 0: every cell is admissible.  band >= 1: cell (i, j) is admissible iff |j (Ta - 1) - i (Tb - 1)| <= band max(Ta - 1, Tb - 1);
+ *   every cell is admissible when Ta == 1 or Tb == 1.  band == 0 is refused.  An inadmissible cell has D = +inf.
+ *   out_dev: double [2] = {D(Ta - 1, Tb - 1), L}.  path_dev: int32 [Ta + Tb - 1][2]; rows 0 .. L - 1 receive the warping path (i, j)
+ *   from (0, 0) to (Ta - 1, Tb - 1), rows past L are left untouched.
+ *   One workgroup walks the lattice along its anti-diagonals, 1024 rows at a time (512 above dim 32); no workgroup waits on another,
+ *   nothing spins, and the backtrace stops after Ta + Tb - 1 steps whatever the features hold.  Two calls give identical bits.
+ *   rvc_dtw_workspace_bytes(Ta, Tb): 8 Tb (the row handed from one pass to the next) + 4 Ta ceil(Tb / 16) (the predecessor of every
+ *   cell, 2 bits each) + 8 (Ta + Tb - 1) (the path backwards), each rounded up to 256: 64.4 MiB at 16384 x 16384.
+ *   Refused: a NULL or misaligned pointer; Ta, Tb or dim outside the limits; band == 0; a workspace below the query's answer.
+ *
+ * rvc_frame_dist_sum_f64: out_dev[0] = sum_{t < T} d(t, t) of the first T frames of a and b (the aligned distortion, no DTW): 256
+ *   partial sums (t mod 256) added in order.  1 <= T <= 2^24, 1 <= dim <= 64.
+ *
+ * rvc_f0_track_sums_f64: two float64 F0 contours of n frames (1 <= n <= 2^27); a frame is voiced when f0 > 0 (NaN: unvoiced).
+ *   out_dev: double [12].  Over the frames voiced in BOTH, with la = log2 a, lb = log2 b, r = 1200 log2(b / a):
+ *     [0] their count  [1] sum r  [2] sum la  [3] sum lb  [4] sum la^2  [5] sum lb^2  [6] sum la lb
+ *     [7] sum (r - rbar)^2 and [8] the count of |r - rbar| > 1200 log2(1.2), rbar = [1] / [0] (a second pass in the same launch)
+ *   [9] frames voiced in a alone  [10] in b alone  [11] in neither.  Every sum is 256 partial sums (frame mod 256) added in order.
+ * All four are asynchronous on `hip_stream` and synchronise nothing. */
+int rvc_melcep_workspace_bytes(int64_t n, int sr, size_t *bytes);
+int rvc_melcep_f32(const float *x_dev, int64_t n, int sr, const float *mel_dev, int n_mels, int n_coef, float *out_dev,
+                   void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+int rvc_dtw_workspace_bytes(int64_t Ta, int64_t Tb, size_t *bytes);
+int rvc_dtw_f64(const float *a_dev, int64_t Ta, const float *b_dev, int64_t Tb, int dim, int64_t band, double *out_dev, int *path_dev,
+                void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+int rvc_frame_dist_sum_f64(const float *a_dev, const float *b_dev, int64_t T, int dim, double *out_dev, void *hip_stream);
+int rvc_f0_track_sums_f64(const double *f0_a_dev, const double *f0_b_dev, int64_t n, double *out_dev, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
