@@ -3,17 +3,21 @@
 //
 // filtfilt(b, a, x) = odd-extend by 18 samples, lfilter forward from zi*ext[0], lfilter backward from zi*y[-1],
 // crop.  lfilter is a 5-state linear recurrence (transposed direct form II), strictly sequential as written.  It is
-// made parallel by chunking with a warm-up: one thread per chunk of M output samples starts W samples earlier
-// from a zero state (or from the true initial state zi*x0 when the warm-up reaches the start of the signal), runs
-// SciPy's exact float64 operation sequence (no FMA contraction) and only writes its own M samples.  The filter's
-// slowest pole has radius 0.9942, so a state error decays by 0.9942^4096 ~ 4e-11 over the warm-up.
+// made parallel by chunking: one lane per chunk of 512 samples.  The state in front of a chunk is linear in the samples before
+// it, z(i0) = sum_j G[j] x[i0 - 1 - j] (+ S[i0] x[0], the response of scipy's start state zi * x[0]), so ff_state_kernel rebuilds
+// it as a double-double dot product with the responses G = A^j B and S = A^j zi, tabulated on the host per coefficient set and
+// cut after W terms; ff_chunk_kernel then runs SciPy's exact float64 operation sequence (no FMA contraction) over the chunk.
+// W follows the coefficients (FF_TAB_LEVEL below): 4096 for the pipeline's filter, whose slowest pole has radius 0.9942; 9856
+// for 20 Hz at 16 kHz, 12288 for 48 Hz at 48 kHz.  Non-finite, unstable and too slow coefficient sets are refused.
 //
-// Accuracy: this direct-form high-pass is ill-conditioned (five poles within 0.02 of z = 1): two evaluations of the
-// reference's OWN recurrence started 8192 samples apart already differ by 2e-8 (measured with scipy.signal.lfilter),
-// so 2e-8 is the noise floor of the reference result itself.  The kernel agrees with scipy.signal.filtfilt to ~5e-8
-// absolute on +-0.3 signals, below the float32 rounding (6e-8 relative) the audio undergoes right after
-// (pipeline.py:445).  An explicit state-transition scan (A^M) was tried and rejected: the companion matrix is so
-// non-normal (|A^256| ~ 4e7) that the scan is unstable in float64.
+// Accuracy: this direct-form high-pass is ill-conditioned (five poles within 0.02 of z = 1).  Against an 80-bit evaluation of
+// the same filtfilt, scipy.signal.filtfilt's own float64 result is 1e-8 to 8e-8 off on signals of amplitude 0.3 to 1 (20 Hz at
+// 16 kHz: up to 4e-6; 48 Hz at 48 kHz: up to 8e-6).  The kernel stays within 2.9 x SciPy's own error on every signal family of
+// tests/test_filtfilt_gpu.py -- noise, DC, sub-cutoff sines, a step, single impulses -- with the pipeline's coefficients, and
+// within 3.8 x with the other two high-passes (measured on an MI355X; the tests gate at 4 x); below the float32 rounding
+// (6e-8 relative) the audio undergoes right after (pipeline.py:445).  A well-conditioned low-pass and a pure FIR come out
+// at SciPy's own rounding level (errors below 1e-15).  An explicit state-transition scan (A^M) was tried and rejected: the companion matrix is so non-normal
+// (|A^256| ~ 4e7) that the scan is unstable in float64.
 #include <string.h>
 
 #include <mutex>
@@ -199,8 +203,8 @@ __device__ __forceinline__ dd dd_mul_d(double ghi, double glo, double x) {   // 
 }
 
 // z(i0) for chunk `ch` (i0 = ch * chunk): one wave per chunk, lane j0 takes terms j0, j0 + 64, ...; four waves = four consecutive
-// chunks per block, so the 160 KiB table is fetched into a CU's L1 once for four dot products (one wave per block: 328 MB of L2
-// reads per pass, 102 us)
+// chunks per block, so the table (W x 160 bytes: 640 KiB at the pipeline's W = 4096, of which the G half is read) is fetched into
+// a CU's L1 once for four dot products (one wave per block: 328 MB of L2 reads per pass, 102 us, at 480 000 samples and W = 4096)
 // tab: [4][FF_ORD][W]: G hi, G lo, S hi, S lo  (S[i] = A^i zi, i < W)
 constexpr int FF_SW = 4;   // waves (chunks) per block
 __global__ void __launch_bounds__(64 * FF_SW)
@@ -260,55 +264,131 @@ ff_state_kernel(const double *__restrict__ x, int64_t n, const double *__restric
 using namespace rvc;
 
 constexpr int FF_CHUNK = 512;
-constexpr int FF_WARM = 4096;
-static_assert(FF_CHUNK % 32 == 0 && FF_WARM % 32 == 0, "chunk and warm-up are whole step-blocks");
+static_assert(FF_CHUNK % FF_SB == 0, "a chunk is whole step-blocks");
 
-// the state impulse responses of one coefficient set, tabulated on the host in long double, split into double-double, kept in HBM
+// Table length.  The state in front of a chunk is a sum over the W input samples before it, so what the table drops is the
+// response's tail past W.  W follows the coefficients: the responses are tabulated until, for FF_TAB_RUN terms in a row, both
+// envelopes -- max over the five state variables of |G_k[j]| and of |S_k[j]|, each relative to the largest value its response
+// has reached -- lie below FF_TAB_LEVEL; with p the first term of that run, W is the first multiple of 64 past p.  The level is
+// where the 48 Hz / 16 kHz high-pass of the pipeline gets the 4096 terms it has always had (its zi response stands at 1.58e-11
+// at term 4095, its input response at 1.22e-11): the state kernel's time is proportional to W and that filter is the hot path.
+// 20 Hz at 16 kHz gets 9856 terms and 48 Hz at 48 kHz 12288; with 4096 those two were 1.5e-5 to 6e-4 off on audio of
+// amplitude 0.3 to 1, 6 to 550 x SciPy's own error (tests/test_filtfilt_gpu.py).  Above FF_TERMS_MAX terms (a 21 MB table) the call is refused.
+constexpr int FF_TERMS_MAX = 1 << 17;
+constexpr double FF_TAB_LEVEL = 2e-11;
+constexpr int FF_TAB_RUN = 64;
+
+// the state impulse responses of one coefficient set, tabulated on the host, split into double-double, kept in HBM
 namespace {
+// The tabulation runs the same ill-conditioned recurrence as the filter (|A^256| ~ 4e7): in plain long double its entries came out
+// 6e-12 of the response's peak off, the size of the tail the table drops, and a 5 Hz sine of amplitude 1 ended 4.2 x SciPy's own
+// error from the extended-precision answer (2.9 x with exact entries).  So the recurrence is carried in pairs of long doubles
+// (~128 significant bits; error-free sum, Dekker product: x87 has no fused multiply-add), far more than the 106 bits kept.
+struct ll { long double hi, lo; };
+inline ll ll_two_sum(long double a, long double b) {
+    const long double s = a + b, bb = s - a;
+    return ll{s, (a - (s - bb)) + (b - bb)};
+}
+inline ll ll_sub(ll a, ll b) {
+    ll s = ll_two_sum(a.hi, -b.hi);
+    const long double lo = s.lo + (a.lo - b.lo);
+    const long double hi = s.hi + lo;
+    return ll{hi, lo - (hi - s.hi)};
+}
+inline ll ll_mul_d(ll a, double bd) {      // a * bd.  a.hi = ah + al (32 + 32 bits), bd = bh + bl (32 + 21 bits): the partial products are exact
+    const long double b = bd, p = a.hi * b, split = 4294967297.0L;          // 2^32 + 1
+    long double t = split * a.hi;
+    const long double ah = t - (t - a.hi), al = a.hi - ah;
+    t = split * b;
+    const long double bh = t - (t - b), bl = b - bh;
+    const long double e = (((ah * bh - p) + ah * bl) + al * bh) + al * bl + a.lo * b;
+    const long double hi = p + e;
+    return ll{hi, e - (hi - p)};
+}
+
 struct FfTable {
     double key[17];
     int device = -1;
+    int W = 0;
     double *dev = nullptr;
 };
 std::mutex g_ff_mu;
 std::vector<FfTable> g_ff_tables;
 
-int ff_table_for(const double *coef_host, const double **out) {
+// Checks coef_host (b[6], a[6], zi[5]) and sizes its table: 0 and *W_out, or the error set in fn's name.  tab, when asked for, is
+// filled as [4][FF_ORD][W]: G hi, G lo, S hi, S lo.
+int ff_tabulate(const char *fn, const double *coef_host, int *W_out, std::vector<double> *tab) {
+    const double *b = coef_host, *a = coef_host + 6, *zi = coef_host + 12;
+    for (int k = 0; k < 17; ++k)
+        if (!isfinite(coef_host[k])) return fail("%s: non-finite coefficient", fn);
+    if (a[0] != 1.0) return fail("%s: a[0] must be 1", fn);
+    double rho = 0.0;
+    if (!pole_radius(a, &rho)) return fail("%s: the poles of a[] could not be found", fn);
+    if (!(rho < 1.0)) return fail("%s: unstable filter (pole radius %.9g)", fn, rho);
+    ll gv[FF_ORD], sv[FF_ORD];
+    for (int i = 0; i < FF_ORD; ++i) {
+        gv[i] = ll_sub(ll{(long double)b[i + 1], 0}, ll_mul_d(ll{(long double)b[0], 0}, a[i + 1]));   // z' = A z + B x with y = z0 + b0 x
+        sv[i] = ll{(long double)zi[i], 0};
+    }
+    auto step = [&](ll *v) {      // v <- A v: v'_i = v_{i+1} - a_{i+1} v_0, v'_4 = -a_5 v_0
+        const ll v0 = v[0];
+        for (int i = 0; i < FF_ORD - 1; ++i) v[i] = ll_sub(v[i + 1], ll_mul_d(v0, a[i + 1]));
+        v[FF_ORD - 1] = ll_sub(ll{0, 0}, ll_mul_d(v0, a[FF_ORD]));
+    };
+    std::vector<double> resp;              // [j][G, S][k][hi, lo]: every entry as a double-double
+    const long double level = (long double)FF_TAB_LEVEL;
+    long double max_g = 0, max_s = 0;
+    int W = 0, run = 0;
+    for (int j = 0; j < FF_TERMS_MAX && !W; ++j) {
+        long double eg = 0, es = 0;
+        for (int k = 0; k < FF_ORD; ++k) { eg = fmaxl(eg, fabsl(gv[k].hi)); es = fmaxl(es, fabsl(sv[k].hi)); }
+        max_g = fmaxl(max_g, eg);
+        max_s = fmaxl(max_s, es);
+        if (tab)
+            for (const ll *v : {gv, sv})
+                for (int k = 0; k < FF_ORD; ++k) {
+                    const double hi = (double)v[k].hi;
+                    resp.push_back(hi);
+                    resp.push_back((double)((v[k].hi - (long double)hi) + v[k].lo));
+                }
+        run = (eg <= level * max_g && es <= level * max_s) ? run + 1 : 0;
+        if (run == FF_TAB_RUN) W = ((j - (FF_TAB_RUN - 1)) / 64 + 1) * 64;       // <= j + 1: every one of them is tabulated
+        step(gv);
+        step(sv);
+    }
+    if (!W)
+        return fail("%s: pole radius %.9g: the responses have not fallen to %.1e of their peaks within %d table terms", fn, rho,
+                    FF_TAB_LEVEL, FF_TERMS_MAX);
+    *W_out = W;
+    if (tab) {
+        tab->assign((size_t)4 * FF_ORD * W, 0.0);
+        for (int j = 0; j < W; ++j)
+            for (int which = 0; which < 2; ++which)
+                for (int k = 0; k < FF_ORD; ++k) {
+                    const double *e = &resp[(((size_t)j * 2 + which) * FF_ORD + k) * 2];
+                    (*tab)[((size_t)(2 * which) * FF_ORD + k) * W + j] = e[0];
+                    (*tab)[((size_t)(2 * which + 1) * FF_ORD + k) * W + j] = e[1];
+                }
+    }
+    return 0;
+}
+
+int ff_table_for(const double *coef_host, const double **out, int *W_out) {
     int device = 0;
     RVC_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> g(g_ff_mu);
     for (const FfTable &t : g_ff_tables)
-        if (t.device == device && memcmp(t.key, coef_host, sizeof(t.key)) == 0) { *out = t.dev; return 0; }
-    const int W = FF_WARM;
-    std::vector<double> tab((size_t)4 * FF_ORD * W);
-    const double *b = coef_host, *a = coef_host + 6, *zi = coef_host + 12;
-    long double gv[FF_ORD], sv[FF_ORD];
-    for (int i = 0; i < FF_ORD; ++i) {
-        gv[i] = (long double)b[i + 1] - (long double)a[i + 1] * (long double)b[0];   // z' = A z + B x with y = z0 + b0 x
-        sv[i] = (long double)zi[i];
-    }
-    auto put = [&](int which, int k, int j, long double v) {
-        const double hi = (double)v;
-        tab[((size_t)(2 * which) * FF_ORD + k) * W + j] = hi;
-        tab[((size_t)(2 * which + 1) * FF_ORD + k) * W + j] = (double)(v - (long double)hi);
-    };
-    auto step = [&](long double *v) {      // v <- A v: v'_i = v_{i+1} - a_{i+1} v_0, v'_4 = -a_5 v_0
-        const long double v0 = v[0];
-        for (int i = 0; i < FF_ORD - 1; ++i) v[i] = v[i + 1] - (long double)a[i + 1] * v0;
-        v[FF_ORD - 1] = -(long double)a[FF_ORD] * v0;
-    };
-    for (int j = 0; j < W; ++j) {
-        for (int k = 0; k < FF_ORD; ++k) { put(0, k, j, gv[k]); put(1, k, j, sv[k]); }
-        step(gv);
-        step(sv);
-    }
+        if (t.device == device && memcmp(t.key, coef_host, sizeof(t.key)) == 0) { *out = t.dev; *W_out = t.W; return 0; }
+    std::vector<double> tab;
     FfTable t;
+    if (ff_tabulate("rvc_filtfilt_order5", coef_host, &t.W, &tab)) return 1;
     memcpy(t.key, coef_host, sizeof(t.key));
     t.device = device;
     RVC_HIP(hipMalloc((void **)&t.dev, tab.size() * sizeof(double)));
     RVC_HIP(hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     g_ff_tables.push_back(t);
     *out = t.dev;
+    *W_out = t.W;
     return 0;
 }
 }  // namespace
@@ -317,6 +397,14 @@ extern "C" int rvc_filtfilt_workspace_bytes(int64_t n, size_t *bytes) {
     if (!bytes || n <= FF_PAD) return fail("rvc_filtfilt_workspace_bytes: bad argument");
     const int64_t ne = n + 2 * FF_PAD;
     *bytes = align_up((size_t)ne * 8, 256) * 2 + align_up((size_t)ceil_div(ne, FF_CHUNK) * FF_ORD * 8, 256);
+    return 0;
+}
+
+extern "C" int rvc_filtfilt_order5_terms(const double *coef_host, int64_t *terms) {
+    if (!coef_host || !terms) return fail("rvc_filtfilt_order5_terms: null pointer");
+    int W = 0;
+    if (ff_tabulate("rvc_filtfilt_order5_terms", coef_host, &W, nullptr)) return 1;
+    *terms = W;
     return 0;
 }
 
@@ -334,14 +422,15 @@ extern "C" int rvc_filtfilt_order5(const double *x_dev, int64_t n, const double 
     memcpy(c.zi, coef_host + 12, sizeof(c.zi));
     if (c.a[0] != 1.0) return fail("rvc_filtfilt_order5: a[0] must be 1");
     const double *tab = nullptr;
-    if (ff_table_for(coef_host, &tab)) return 1;
+    int W = 0;
+    if (ff_table_for(coef_host, &tab, &W)) return 1;      // refuses non-finite, unstable and too slow coefficient sets
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t ne = n + 2 * FF_PAD, n_chunks = ceil_div(ne, FF_CHUNK);
     double *yf = (double *)workspace_dev;
     double *zstate = (double *)((char *)workspace_dev + align_up((size_t)ne * 8, 256) * 2);
     const dim3 grid((unsigned)ceil_div(n_chunks, 64)), block(64);
     for (int backward = 0; backward < 2; ++backward) {
-        hipLaunchKernelGGL(ff_state_kernel, dim3((unsigned)ceil_div(n_chunks, FF_SW)), dim3(64 * FF_SW), 0, stream, x_dev, n, yf, backward, c, FF_CHUNK, FF_WARM, n_chunks, tab, zstate);
+        hipLaunchKernelGGL(ff_state_kernel, dim3((unsigned)ceil_div(n_chunks, FF_SW)), dim3(64 * FF_SW), 0, stream, x_dev, n, yf, backward, c, FF_CHUNK, W, n_chunks, tab, zstate);
         RVC_LAUNCH_CHECK();
         hipLaunchKernelGGL(ff_chunk_kernel, grid, block, 0, stream, x_dev, n, yf, backward, c, FF_CHUNK, 0, n_chunks, yf, y_dev, zstate);
         RVC_LAUNCH_CHECK();

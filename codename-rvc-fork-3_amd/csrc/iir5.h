@@ -1,7 +1,10 @@
 // The 5th-order float64 recurrence step and the LDS tile movement shared by K6 (filtfilt.hip: zero-phase high-pass of the
 // inference pipeline) and K17 (preprocess.hip: the causal high-pass of the dataset preprocessor).  Both run one lane per chunk
-// of consecutive samples, 64 chunks per wave, and move their samples through LDS in [64 chunks] x [FF_SB steps] tiles.
+// of consecutive samples, 64 chunks per wave, and move their samples through LDS in [64 chunks] x [FF_SB steps] tiles.  Both size
+// what stands in front of a chunk from the filter's poles (pole_radius, host side).
 #pragma once
+
+#include <math.h>
 
 #include "common.h"
 
@@ -34,6 +37,53 @@ __device__ __forceinline__ double ff_step(const FiltCoef &c, double xv, double z
     for (int i = 0; i < FF_ORD - 1; ++i) z[i] = t[i] - ya[i];
     z[FF_ORD - 1] = xb[FF_ORD] - ya[FF_ORD - 1];
     return y;
+}
+
+// largest root radius of z^5 + a[1] z^4 + ... + a[5] (Durand-Kerner in long double; the five Butterworth poles are simple).
+// Host side: K17 sizes its warm-up from it, K6 refuses unstable filters with it and names it when a table would be too long.
+inline bool pole_radius(const double *a, double *rho_out) {
+    typedef long double L;
+    L re[FF_ORD], im[FF_ORD];
+    for (int k = 0; k < FF_ORD; ++k) {   // start values on a circle, at no symmetric position
+        const L ang = 0.4L + 2.0L * 3.14159265358979323846L * k / FF_ORD;
+        re[k] = 0.9L * cosl(ang);
+        im[k] = 0.9L * sinl(ang);
+    }
+    for (int it = 0; it < 500; ++it) {
+        L moved = 0;
+        for (int k = 0; k < FF_ORD; ++k) {
+            L pr = 1, pi = 0;                         // p(z_k), Horner
+            for (int c = 1; c <= FF_ORD; ++c) {
+                const L nr = pr * re[k] - pi * im[k] + (L)a[c], ni = pr * im[k] + pi * re[k];
+                pr = nr;
+                pi = ni;
+            }
+            L dr = 1, di = 0;                         // prod_{j != k} (z_k - z_j)
+            for (int j = 0; j < FF_ORD; ++j) {
+                if (j == k) continue;
+                const L er = re[k] - re[j], ei = im[k] - im[j];
+                const L nr = dr * er - di * ei, ni = dr * ei + di * er;
+                dr = nr;
+                di = ni;
+            }
+            const L den = dr * dr + di * di;
+            if (!(den > 0)) return false;
+            const L qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
+            re[k] -= qr;
+            im[k] -= qi;
+            moved = fmaxl(moved, fabsl(qr) + fabsl(qi));
+        }
+        if (!(moved == moved)) return false;          // NaN
+        // converged to the rounding noise of p(z) over the cluster's separations (~1e-8 of a pole 2e-3 inside the circle at
+        // 48 kHz: nothing against the rule's 53 bits); the iteration is quadratic from here, one more step would only jitter
+        if (moved < 1e-6L) {
+            L best = 0;
+            for (int k = 0; k < FF_ORD; ++k) best = fmaxl(best, sqrtl(re[k] * re[k] + im[k] * im[k]));
+            *rho_out = (double)best;
+            return true;
+        }
+    }
+    return false;
 }
 
 // One wave = 64 consecutive chunks, one lane per chunk.  A lane walks its chunk sequentially, so a naive load touches

@@ -185,52 +185,6 @@ slice_export_kernel(const double *__restrict__ x, int64_t n, const int64_t *__re
     lo[g] = (float)acc;
 }
 
-// largest root radius of z^5 + a[1] z^4 + ... + a[5] (Durand-Kerner in long double; the five Butterworth poles are simple)
-static bool pole_radius(const double *a, double *rho_out) {
-    typedef long double L;
-    L re[FF_ORD], im[FF_ORD];
-    for (int k = 0; k < FF_ORD; ++k) {   // start values on a circle, at no symmetric position
-        const L ang = 0.4L + 2.0L * 3.14159265358979323846L * k / FF_ORD;
-        re[k] = 0.9L * cosl(ang);
-        im[k] = 0.9L * sinl(ang);
-    }
-    for (int it = 0; it < 500; ++it) {
-        L moved = 0;
-        for (int k = 0; k < FF_ORD; ++k) {
-            L pr = 1, pi = 0;                         // p(z_k), Horner
-            for (int c = 1; c <= FF_ORD; ++c) {
-                const L nr = pr * re[k] - pi * im[k] + (L)a[c], ni = pr * im[k] + pi * re[k];
-                pr = nr;
-                pi = ni;
-            }
-            L dr = 1, di = 0;                         // prod_{j != k} (z_k - z_j)
-            for (int j = 0; j < FF_ORD; ++j) {
-                if (j == k) continue;
-                const L er = re[k] - re[j], ei = im[k] - im[j];
-                const L nr = dr * er - di * ei, ni = dr * ei + di * er;
-                dr = nr;
-                di = ni;
-            }
-            const L den = dr * dr + di * di;
-            if (!(den > 0)) return false;
-            const L qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
-            re[k] -= qr;
-            im[k] -= qi;
-            moved = fmaxl(moved, fabsl(qr) + fabsl(qi));
-        }
-        if (!(moved == moved)) return false;          // NaN
-        // converged to the rounding noise of p(z) over the cluster's separations (~1e-8 of a pole 2e-3 inside the circle at
-        // 48 kHz: nothing against the rule's 53 bits); the iteration is quadratic from here, one more step would only jitter
-        if (moved < 1e-6L) {
-            L best = 0;
-            for (int k = 0; k < FF_ORD; ++k) best = fmaxl(best, sqrtl(re[k] * re[k] + im[k] * im[k]));
-            *rho_out = (double)best;
-            return true;
-        }
-    }
-    return false;
-}
-
 constexpr int64_t LF_WARM_MAX = (int64_t)1 << 22;
 
 // the warm-up rule of the header comment; 0 with the error set when the filter is unusable

@@ -74,6 +74,7 @@ SYMBOLS = {
     "rvc_resample_poly_f64": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "rvc_filtfilt_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
     "rvc_filtfilt_order5": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rvc_filtfilt_order5_terms": (c_int, [c_void_p, POINTER(c_int64)]),
     "rvc_bigru_workspace_bytes": (c_int, [c_int, POINTER(c_size_t)]),
     "rvc_bigru_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_size_t,
                                   c_void_p]),
@@ -566,8 +567,17 @@ def _filtfilt_coef(b, a):
     return _ff_coef_cache[key]
 
 
+def filtfilt_terms(b, a) -> int:
+    """The length of the state table rvc_filtfilt_order5 keeps for these coefficients: the input samples in front of a chunk that
+    its start state is summed over."""
+    coef, terms = _filtfilt_coef(b, a), c_int64()
+    _check(_lib.rvc_filtfilt_order5_terms(coef.ctypes.data, ctypes.byref(terms)), "rvc_filtfilt_order5_terms")
+    return terms.value
+
+
 def filtfilt_order5(x: torch.Tensor, b, a) -> torch.Tensor:
-    """scipy.signal.filtfilt(b, a, x) for a 5th-order filter; x: 1-D float64 on the device."""
+    """scipy.signal.filtfilt(b, a, x) for a 5th-order filter; x: 1-D float64 on the device.  Non-finite, unstable and too slow
+    coefficient sets are refused by the library."""
     if not x.is_cuda or x.dtype != torch.float64 or x.dim() != 1:
         raise NativeError("filtfilt_order5 wants a 1-D float64 HBM tensor")
     x = x.contiguous()

@@ -137,9 +137,13 @@ int rvc_resample_poly_f64(const double *x_dev, int64_t n_in, int up, int down, c
  * Replaces `signal.filtfilt(bh, ah, audio)` (rvc/infer/pipeline.py:562; 5th-order Butterworth, pipeline.py:23-28)
  * with SciPy's defaults (padtype "odd", padlen 18, lfilter_zi initial conditions), float64, on the device.
  * coef_host (host memory, 17 doubles): b[6], a[6] (a[0] == 1), zi[5] = scipy.signal.lfilter_zi(b, a).
- * x_dev, y_dev: [n] float64 (must not alias).  Agrees with SciPy to the conditioning of the recurrence (~5e-8,
- * see csrc/filtfilt.hip). */
+ * x_dev, y_dev: [n] float64 (must not alias), n > 18.  Every chunk of 512 samples starts from a state summed over the `terms`
+ * samples in front of it with a tabulated response; `terms` follows the coefficients (4096 for the pipeline's filter, more for
+ * slower poles; rvc_filtfilt_order5_terms returns it, host only).  Refused: a non-finite coefficient, a[0] != 1, a pole on or
+ * outside the unit circle, poles so slow that the table would pass 2^17 terms.  A refused call writes nothing.  Agrees with an
+ * extended-precision evaluation to within a few times SciPy's own float64 error on the same input (csrc/filtfilt.hip). */
 int rvc_filtfilt_workspace_bytes(int64_t n, size_t *bytes);
+int rvc_filtfilt_order5_terms(const double *coef_host, int64_t *terms);
 int rvc_filtfilt_order5(const double *x_dev, int64_t n, const double *coef_host, double *y_dev,
                         void *workspace_dev, size_t workspace_bytes, void *stream);
 
